@@ -15,6 +15,8 @@ Prints ONE JSON line (rank 0).  `roofline` prices the decode kernel against the 
 peak with the ALGORITHMIC bytes (3192 B per FIC frame: 3096 symbol bytes in + 96 out);
 `cpu_baseline` is this repo's own AVX2 port of the same integer specification
 (oracle/vit_avx2.c, "port") timed on the host cores of the same box, on the same frames.
+`--dump-outputs DIR` writes what the last timed step decoded to DIR (dump_outputs), so that two builds can be
+compared output for output on the same seeded inputs.
 """
 import argparse
 import json
@@ -38,6 +40,7 @@ FRAMEBITS = 768
 TAIL = 6
 POLYS = (109, 79, 83, 109)  # viterbi-benchmark.cpp:64
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BYTES = 60 * 2 ** 20  # --dump-outputs: data bytes in all (the .npy headers stay well inside 64 MB)
 
 
 def make_frames(nframes, framebits, seed, device, ebn0_db=3.0, return_bits=False, payload_bits=None):
@@ -198,6 +201,22 @@ def second_stage(V, dev, nsf=131072, rsdims=24, distinct=256, iters=100):
             "outputs_and_return_values_as_constructed": ok}
 
 
+def dump_outputs(path, name, out):
+    """--dump-outputs: the output a caller of the timed path receives after its last step (decoded bytes, one row per
+    frame) as DIR/<name>.npy in float32, where every byte value is exact.  An output above DUMP_BYTES keeps a fixed,
+    seeded sample of its rows (the same rows for the same arguments) and their indices go to DIR/<name>_rows.npy."""
+    a = np.asarray(out, dtype=np.float32)
+    os.makedirs(path, exist_ok=True)
+    files = [name + ".npy"]
+    if a.nbytes > DUMP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], DUMP_BYTES // (a.shape[1] * 4 + 8), replace=False))
+        a = a[rows]
+        np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+        files.append(name + "_rows.npy")
+    np.save(os.path.join(path, name + ".npy"), a)
+    return {"dir": path, "files": files, "rows": int(a.shape[0]), "dtype": "float32"}
+
+
 def precondition(launch, ms=150.0):
     """untimed: ~15 ms of sustained load bring the MI355X to its steady-state clocks; a leg that follows seconds of
     GPU idle (the CPU baseline) starts ~10 % slow without it (tools/exp/trend.py)"""
@@ -324,7 +343,14 @@ def parse_args(argv=None):
     ap.add_argument("--stub", action="store_true",
                     help="TEST ONLY: no GPU, the decoder is replaced by a byte-copy stand-in; the JSON line says so "
                          "and its value is not a measurement")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's decoded bytes) to "
+                         "DIR/decoded.npy as float32, at most 64 MB (a larger output: a fixed, seeded sample of rows, "
+                         "their indices in DIR/decoded_rows.npy); the inputs are seeded, so runs compare file for file")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _free_port():
@@ -574,6 +600,10 @@ def main(argv=None):
         dt = float(t.item())
     if args.mode != "shard" and dist and rank == 0 and args.stub:
         routing_ok = bool(torch.equal(d_all_out, d_all[:, :out_len]))  # every frame came back to its own row
+    # the last timed step's output, taken before the legs below reuse the buffers
+    last_out = None
+    if args.dump_outputs and rank == 0:
+        last_out = (d_out if args.mode == "shard" or not dist else d_all_out).to("cpu", copy=True).numpy()
 
     result = None
     if rank == 0:
@@ -666,6 +696,8 @@ def main(argv=None):
                 result["second_stage"] = {"error": "%s: %s" % (type(e).__name__, e)}
         if not args.stub:
             _attach_cached_counters(result)
+        if last_out is not None:
+            result["dump_outputs"] = dump_outputs(args.dump_outputs, "decoded", last_out)
     if dist and world > 1 and args.mode == "shard" and not args.no_scatter_leg:
         # The extra leg is collective: every rank runs it.  It must never cost the run its headline line, so a
         # watchdog ends ALL ranks (rank 0 printing the line with the error in it, exit code 3) if it does not come back.
@@ -739,6 +771,7 @@ def main_multi(args):
     for _ in range(args.steps):
         step()  # synchronous
     dt = time.perf_counter() - t0
+    last_out = d_all_out.cpu().numpy() if args.dump_outputs else None
     ref = torch.zeros_like(d_all_out)
     V.decode_batch_dev(d_all, ref, FRAMEBITS, n_total)
     torch.cuda.synchronize()
@@ -754,6 +787,8 @@ def main_multi(args):
                    "launch": "single process, C ABI"},
         "roofline": None, "multi_matches_single_launch": same,
     }
+    if last_out is not None:
+        result["dump_outputs"] = dump_outputs(args.dump_outputs, "decoded", last_out)
     print(json.dumps(result), flush=True)
     return result
 

@@ -36,6 +36,19 @@ def test_make_frames_is_seeded_and_noisy():
     assert 20 < float(v.std()) < 120 and 0 < int((a == 0).sum()) and 0 < int((a == 255).sum())  # clipped AWGN around 127.5
 
 
+def test_dump_outputs_samples_a_large_output(tmp_path, monkeypatch):
+    """an output above the budget keeps a fixed, seeded sample of its rows, with the row indices next to it"""
+    monkeypatch.setattr(bench, "DUMP_BYTES", 100 * 96 * 4)
+    out = np.random.default_rng(1).integers(0, 256, (1000, 96), dtype=np.uint8)
+    info = bench.dump_outputs(str(tmp_path / "a"), "decoded", out)
+    bench.dump_outputs(str(tmp_path / "b"), "decoded", out)
+    a, rows = np.load(tmp_path / "a" / "decoded.npy"), np.load(tmp_path / "a" / "decoded_rows.npy")
+    assert info["files"] == ["decoded.npy", "decoded_rows.npy"] and a.dtype == np.float32 and rows.dtype == np.float64
+    assert a.nbytes + rows.nbytes <= bench.DUMP_BYTES and len(rows) == a.shape[0] > 90
+    assert np.array_equal(a, out[rows.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(a, np.load(tmp_path / "b" / "decoded.npy"))
+
+
 def test_bench_constants():
     assert bench.FRAMEBITS == 768 and bench.TAIL == 6 and bench.POLYS == (109, 79, 83, 109)
     assert 4 * (bench.FRAMEBITS + bench.TAIL) + bench.FRAMEBITS // 8 == 3192  # SURVEY 8d: algorithmic bytes per FIC frame

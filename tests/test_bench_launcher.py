@@ -93,6 +93,30 @@ def test_under_torch_distributed_run_with_two_ranks():
     assert r["n_gpus"] == 2 and r["config"]["launch"] == "external launcher"
 
 
+def test_dump_outputs_holds_the_last_step_and_repeats(tmp_path):
+    """--dump-outputs DIR: what the last timed step computed, as float32 .npy, the same file for the same arguments;
+    --steps sets the timed steps.  The byte-copy stand-in's output is the first bytes of every frame, so the expected
+    file is known: one process (rank 0's d_out) and two ranks in scatter mode (rank 0 holds the whole stream)."""
+    import numpy as np
+    import torch
+    import bench
+    dumps = []
+    for d in ("a", "b"):
+        r = _run(["--steps", "3", "--dump-outputs", str(tmp_path / d)])
+        assert r["steps"] == 3 and "ms_per_step" in r and r["dump_outputs"]["files"] == ["decoded.npy"]
+        dumps.append(np.load(tmp_path / d / "decoded.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (48, 96) and np.array_equal(dumps[0], dumps[1])
+    frames = bench.make_frames(48, bench.FRAMEBITS, seed=1234, device=torch.device("cpu"))
+    assert np.array_equal(dumps[0], frames[:, :96].numpy().astype(np.float32))
+    r = _run(["--gpus", "2", "--mode", "scatter", "--chunk-frames", "10", "--dump-outputs", str(tmp_path / "c")])
+    assert r["routing_ok"] is True
+    frames = bench.make_frames(96, bench.FRAMEBITS, seed=99, device=torch.device("cpu"))
+    assert np.array_equal(np.load(tmp_path / "c" / "decoded.npy"), frames[:, :96].numpy().astype(np.float32))
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--stub", "--steps", "0"],
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 2 and "--steps must be at least 1" in p.stderr
+
+
 def test_second_stage_input_generator_agrees_with_the_oracle():
     """bench.py builds its RS(120,110) superframes from the code's definition (it may not use the oracle for its
     product-side legs); here the oracle decodes them: valid codewords, one correction per injected error."""

@@ -134,6 +134,17 @@ def test_bench_through_its_spawn_path(torch_cuda):
     assert r["n_gpus"] == 1 and r["value"] > 500 and r["multi_matches_single_launch"] is True
 
 
+def test_bench_dump_outputs_are_the_decoded_frames(O, torch_cuda, tmp_path):
+    """--dump-outputs: the file holds what the timed path decoded from bench.py's seeded frames, bit for bit"""
+    sys.path.insert(0, ROOT)
+    import bench
+    r = _bench(["--frames", "8192", "--no-rs", "--no-pipelined", "--no-sensitivity", "--dump-outputs", str(tmp_path)])
+    assert r["steps"] == 3 and r["dump_outputs"]["files"] == ["decoded.npy"]
+    got = np.load(tmp_path / "decoded.npy")
+    sym = bench.make_frames(8192, bench.FRAMEBITS, seed=1234, device=torch_cuda.device("cuda", 0)).cpu().numpy()
+    assert got.dtype == np.float32 and np.array_equal(got, O.decode_batch(bench.FRAMEBITS, sym, nthreads=8).astype(np.float32))
+
+
 def test_device_index_out_of_range_fails_loudly(torch_cuda):
     """VITERBI_AMD_DEVICE beyond the usable gfx950 devices: no silent fall-back to another GPU (round-1 advisor finding)"""
     code = ("import sys; sys.path.insert(0, %r); import numpy as np, _vitpkg; V = _vitpkg.load_package();"

@@ -4,7 +4,7 @@
 # usage: tools/collect_config_profiles.sh <round-tag>
 set -u
 TAG=${1:-r01}
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/configs_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -6,7 +6,7 @@
 # usage: tools/collect_profiles.sh <round-tag>
 set -u
 TAG=${1:-r01}
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/profiles_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B two builds of libviterbi.so on the same box: alternating runs of the headline bench kernel time
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 for i in 1 2 3; do
   for v in base "$@"; do
     if [ "$v" = base ]; then unset VITERBI_AMD_LIB; else export VITERBI_AMD_LIB=$R/tools/exp/libviterbi_$v.so; fi

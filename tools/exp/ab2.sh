@@ -1,6 +1,6 @@
 #!/bin/bash
 # like ab.sh, plus the 524288-frame batch (steady state) per variant
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 for i in 1 2; do
   for v in base "$@"; do
     if [ "$v" = base ]; then unset VITERBI_AMD_LIB; else export VITERBI_AMD_LIB=$R/tools/exp/libviterbi_$v.so; fi

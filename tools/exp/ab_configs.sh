@@ -1,6 +1,6 @@
 #!/bin/bash
 # alternating runs of tests/tools/bench_configs.py (decode cases only) over library variants
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 for i in 1 2; do
   for v in "$@"; do
     if [ "$v" = base ]; then unset VITERBI_AMD_LIB; else export VITERBI_AMD_LIB=$R/tools/exp/libviterbi_$v.so; fi

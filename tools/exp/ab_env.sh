@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B by environment: alternating runs of the headline bench, "name=VAR=value" pairs; e.g. ab_env.sh pk4=VITERBI_AMD_PK8=0 pk8=VITERBI_AMD_PK8=1
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 EXTRA=${AB_BENCH_ARGS:-}
 for i in 1 2 3; do
   for v in "$@"; do

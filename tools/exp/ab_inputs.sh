@@ -1,7 +1,7 @@
 #!/bin/bash
 # alternating runs of tests/tools/bench_inputs.py (configs 2 and 3 x four input families) over library variants:
 #   ab_inputs.sh <variant...>   (base = the product library; tools/exp/libviterbi_<name>.so otherwise)
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 for i in 1 2; do
   for v in "$@"; do
     if [ "$v" = base ]; then unset VITERBI_AMD_LIB; else export VITERBI_AMD_LIB=$R/tools/exp/libviterbi_$v.so; fi

@@ -1,7 +1,7 @@
 #!/bin/bash
 # alternating runs of the headline bench over library variants (tools/exp/libviterbi_<name>.so; "base" = the product library)
 # with the environment given in AB_ENV (e.g. AB_ENV="VITERBI_AMD_PK8=1")
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 for i in 1 2 3; do
   for v in "$@"; do
     if [ "$v" = base ]; then L=$R/viterbi.dll_amd/libviterbi.so; else L=$R/tools/exp/libviterbi_$v.so; fi

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of library variants on the RS kernel: tests/tools/bench_rs.py over the error mixes, 131072 and 16384 superframes
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 for v in base "$@"; do
   if [ "$v" = base ]; then unset VITERBI_AMD_LIB; else export VITERBI_AMD_LIB=$R/tools/exp/libviterbi_$v.so; fi
   for m in clean light rough le2 le3 le5 mixed; do

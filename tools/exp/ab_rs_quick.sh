@@ -1,6 +1,6 @@
 #!/bin/bash
 # quick A/B of library variants on the RS kernel: ab_rs_quick.sh "<modes>" <variant...>  (base = the product library)
-R=${GRAFT_REPO_ROOT:-/root/repo}; MODES=$1; shift
+R=$(cd "$(dirname "$0")/../.." && pwd); MODES=$1; shift
 for i in 1 2; do
 for v in "$@"; do
   if [ "$v" = base ]; then unset VITERBI_AMD_LIB; else export VITERBI_AMD_LIB=$R/tools/exp/libviterbi_$v.so; fi

@@ -1,6 +1,6 @@
 #!/bin/bash
 # alternating runs of tools/exp/sizes.py (kernel 2 = packed, by framebits:frames in SIZES) over library variants
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 for i in 1 2; do
   for v in "$@"; do
     if [ "$v" = base ]; then unset VITERBI_AMD_LIB; else export VITERBI_AMD_LIB=$R/tools/exp/libviterbi_$v.so; fi

@@ -1,7 +1,7 @@
 """Config 3 (32768 frames, 288 ... 6912 bits): the descriptor entry as called (device sort, split gate, side stream) against the same table
 sorted on the HOST and launched with VITERBI_AMD_NO_SORT=1 (no sort launches, no second kernel, no fork/join): the launcher's overhead."""
 import json, os, sys, subprocess
-ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if len(sys.argv) == 1:
     for mode in ("device_sort", "host_sorted"):
         env = dict(os.environ)

@@ -3,7 +3,7 @@ in-flight parts inside), the in-flight parts alone (round-4 builds; the round-3 
 after the forward pass.  usage: long_phases.py framebits frames [round3]"""
 import ctypes, json, os, sys
 import numpy as np, torch
-ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import _vitpkg
 from bench import make_frames

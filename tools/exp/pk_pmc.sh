@@ -1,7 +1,7 @@
 #!/bin/bash
 # per-wave instruction / issue counters of the packed decode kernel of the headline bench, per configuration:
 #   pk_pmc.sh name=ENVVAR=value ...   (e.g. pk4=VITERBI_AMD_PK8=0 pk8=VITERBI_AMD_PK8=1; VITERBI_AMD_LIB=... works too)
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 OUT=$R/gpurun_out/pk_pmc; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
 for v in "$@"; do
   name=${v%%=*}; kv=${v#*=}

@@ -1,6 +1,6 @@
 #!/bin/bash
 # per-wave SQ counters of the kernels matching <pattern> while running a command: pmc_cmd.sh <tag> <pattern> <python-script> [args...]
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 TAG=$1; PAT=$2; shift 2
 OUT=$R/gpurun_out/pmc_cmd; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY --output-format csv -d $OUT/$TAG -- python3 "$@" > $OUT/$TAG.log 2>&1

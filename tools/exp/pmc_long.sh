@@ -1,6 +1,6 @@
 #!/bin/bash
 # SQ counters of the packed kernels by launch (tools/exp/sizes.py: FIC and long frames, one round and five): VALU / LDS / wait profile of the long-frame kernel
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 OUT=$R/gpurun_out/pmc_long; rm -rf $OUT; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
 for S in ${PMC_SIZES:-768:65536 3072:16384 3072:81920 6912:36400}; do
 export SIZES=$S

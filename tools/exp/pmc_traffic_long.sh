@@ -2,7 +2,7 @@
 # HBM traffic of the long-frame kernel per launch, by (framebits:frames), for the library in VITERBI_AMD_LIB (default: the product):
 # rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over tools/exp/sizes.py; HBM bytes = 2*FETCH_SIZE*1024 (gfx950
 # correction, MI355X_MICROARCH.md) + WRITE_SIZE*1024; algorithmic bytes = frames * (4*(framebits+6) + framebits/8).
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 OUT=$R/gpurun_out/pmc_traffic_long; rm -rf $OUT; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
 for S in ${PMC_SIZES:-4608:81920 6912:36400 6912:7280 3072:81920}; do
 export SIZES=$S

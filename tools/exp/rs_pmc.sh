@@ -1,6 +1,6 @@
 #!/bin/bash
 # per-wave instruction and LDS counters of rs_kernel for one error mix, per library variant: rs_pmc.sh <mode> <variant...>
-R=${GRAFT_REPO_ROOT:-/root/repo}; MODE=$1; shift
+R=$(cd "$(dirname "$0")/../.." && pwd); MODE=$1; shift
 OUT=$R/gpurun_out/rs_pmc; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
 for v in "$@"; do
   if [ "$v" = base ]; then unset VITERBI_AMD_LIB; else export VITERBI_AMD_LIB=$R/tools/exp/libviterbi_$v.so; fi

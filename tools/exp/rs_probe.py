@@ -1,6 +1,6 @@
 import json, os, sys, time
 import numpy as np, torch
-ROOT = os.environ.get("GRAFT_REPO_ROOT", "/root/repo"); sys.path.insert(0, ROOT)
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT)
 import _vitpkg
 from bench import make_frames, rs_encode_columns  # the encoder is bench.py's own (no oracle outside tests/)
 V = _vitpkg.load_package(); V.initialize()

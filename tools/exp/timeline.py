@@ -2,7 +2,7 @@
 of every workgroup (s_memtime, 100 MHz) -> rounds, spread, drain.  usage: python tools/exp/timeline.py [frames] [noisy|random] [framebits]"""
 import ctypes, json, os, sys
 import numpy as np, torch
-ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 os.environ["VITERBI_AMD_LIB"] = os.path.join(ROOT, "tools", "exp", "libviterbi_times.so")
 import _vitpkg

@@ -1,5 +1,5 @@
 #!/bin/bash
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/../.." && pwd)
 OUT=$R/gpurun_out/trace_cfg3; rm -rf $OUT; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
 rocprofv3 --kernel-trace --output-format csv -d $OUT/kt -- python3 $R/tools/exp/cfg3_overhead.py device_sort > $OUT/log.txt 2>&1
 python3 - $OUT <<'PY'

@@ -1,5 +1,5 @@
 import sys, os, json, time
-sys.path.insert(0, '/root/repo' if os.path.isdir('/root/repo/tests') else os.environ.get('GRAFT_REPO_ROOT','.'))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch, _vitpkg
 from bench import make_frames
 V=_vitpkg.load_package(); V.initialize(); V.set_kernel(2)
