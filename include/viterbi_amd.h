@@ -179,6 +179,51 @@ int vit_set_batch_min_callers(int min_callers);
 int vit_set_batch_depth(int launches_in_flight);
 int vit_set_batch_spin_cpus(int cpus);
 
+/* Punctured input (EN 300 401 clause 11: FIC, EEP/UEP MSC sub-channels, DAB+).  The K=7 rate-1/4 mother code's output is
+ * thinned by puncturing vectors; these calls take the transmitted symbols only and write the erasures in on the device
+ * before decoding.  A profile is a run of segments; segment k covers `steps` trellis steps and starts its 8-step pattern
+ * period afresh at its own first step (it may end mid-period).  keep bit 4*(k mod 8) + j = symbol j of the segment's
+ * k-th step is transmitted (symbol order within a step as in the u8 device format; 0 = punctured, replaced by the
+ * erasure value).  A puncturing vector v0...v31 over a 32-bit sub-block is keep = sum v_i << i, i.e. 8 steps; a DAB
+ * block of 128 bits is 32 steps under one vector; the 6 tail steps form a segment of their own (low 24 bits of keep).
+ * A step whose four symbols are all punctured is legal.  The library compiles in no tables of the standard: the
+ * caller supplies the vectors (INTEGRATION.md shows the FIC).  Transmitted symbols are one byte each, back to back in
+ * step order. */
+#define VIT_PUNCT_MAX_SEGS 8
+typedef struct vit_punct_seg {
+    uint32_t steps; /* trellis steps this segment covers (>= 1) */
+    uint32_t keep;  /* period-8-step mask, see above */
+} vit_punct_seg;
+typedef struct vit_punct_profile {
+    uint32_t nsegs; /* 1 ... VIT_PUNCT_MAX_SEGS */
+    vit_punct_seg seg[VIT_PUNCT_MAX_SEGS];
+} vit_punct_profile;
+/* Transmitted symbols of one frame under `p`, or -1 if p is invalid or its steps do not sum to
+ * framebits + 6.  Host only, needs no GPU. */
+int64_t vit_punctured_length(const vit_punct_profile *p, uint32_t framebits);
+/* nframes equal-length frames, frame f's transmitted symbols at f*P bytes (P = vit_punctured_length);
+ * no alignment requirement on d_punct or P.  Missing symbols become `erasure`.  Decoded output as
+ * vit_decode_batch_dev.  Returns VIT_ERR_ARG for an invalid profile or one that does not cover
+ * framebits + 6 steps.  `profile` is a HOST pointer, read during the call.
+ * The expanded symbols go to the calling thread's scratch buffer on the caller's current device (the one the u32
+ * path narrows into): it grows to nframes*4*(framebits+6) bytes; its reuse across streams is ordered by an event. */
+int vit_decode_punctured_dev(const uint8_t *d_punct, uint8_t *d_decoded, uint32_t framebits,
+                             int64_t nframes, const vit_punct_profile *profile, uint8_t erasure,
+                             void *stream);
+/* Variable-length, per-frame profile: desc[i].reserved = index into the DEVICE array d_profiles
+ * (nprofiles entries); sym_offset = byte offset of the frame's transmitted symbols in d_punct (any
+ * alignment).  Always bounds-checked like vit_decode_varlen_dev_checked: a descriptor with odd or
+ * too large framebits, a profile index >= nprofiles, an invalid profile, a profile whose steps do not
+ * sum to framebits + 6, or input/output bytes outside sym_bytes/out_bytes is skipped - its output
+ * bytes stay untouched.  d_desc and d_profiles are never modified.  No input byte outside a frame's own
+ * [sym_offset, sym_offset + P) is read.  Scratch: frame i is expanded into slot i*4*(max_framebits+6) of the
+ * thread's scratch buffer, which grows to nframes*4*(max_framebits+6) bytes, plus an internal descriptor table of
+ * nframes*24 bytes; the decode then runs as vit_decode_varlen_dev on them (device sort, long-frame kernel). */
+int vit_decode_punctured_varlen_dev(const uint8_t *d_punct, uint64_t sym_bytes, uint8_t *d_decoded,
+                                    uint64_t out_bytes, const vit_frame_desc *d_desc, int64_t nframes,
+                                    uint32_t max_framebits, const vit_punct_profile *d_profiles,
+                                    uint32_t nprofiles, uint8_t erasure, void *stream);
+
 /* Kernel selection (the analogue of the reference's dispatcher, setupdll.cpp:195-270):
  *   0 = auto: launches of up to 2048 frames (they cannot fill the chip) take the latency kernel - one
  *       frame per wavefront, ~20 us per FIC frame -, larger ones the packed throughput kernel;

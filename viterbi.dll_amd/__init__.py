@@ -24,6 +24,7 @@ EXPORTS = [
     "vit_decode_batch_dev",
     "vit_decode_batch_dev_u32", "vit_decode_varlen_dev", "vit_decode_varlen_dev_checked", "vit_pack_symbols_dev", "vit_sort_descs",
     "vit_decode_batch_host", "vit_rs_batch_dev", "vit_rs_batch_host", "vit_dabplus_superframes_dev",
+    "vit_punctured_length", "vit_decode_punctured_dev", "vit_decode_punctured_varlen_dev",
     "vit_decode_stream_multi",
 ]
 MULTI_LOOPBACK = 0x1
@@ -40,6 +41,18 @@ class FrameDesc(C.Structure):
 
 
 DESC_DTYPE = np.dtype([("sym_offset", "<u8"), ("out_offset", "<u8"), ("framebits", "<u4"), ("reserved", "<u4")])
+
+PUNCT_MAX_SEGS = 8
+
+
+class PunctSeg(C.Structure):
+    """vit_punct_seg of include/viterbi_amd.h"""
+    _fields_ = [("steps", C.c_uint32), ("keep", C.c_uint32)]
+
+
+class PunctProfile(C.Structure):
+    """vit_punct_profile of include/viterbi_amd.h (68 bytes; bytes(profile) is its device image)"""
+    _fields_ = [("nsegs", C.c_uint32), ("seg", PunctSeg * PUNCT_MAX_SEGS)]
 
 _lib = None
 
@@ -87,6 +100,11 @@ def lib():
         L.vit_rs_batch_host.argtypes = [vp, vp, vp, C.c_uint32, C.c_int64]
         L.vit_dabplus_superframes_dev.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_int64, vp]
         L.vit_decode_stream_multi.argtypes = [vp, vp, C.c_uint32, C.c_int64, vp, C.c_int, C.c_int64, C.c_int64, C.c_uint, vp]
+        L.vit_punctured_length.argtypes = [C.POINTER(PunctProfile), C.c_uint32]
+        L.vit_punctured_length.restype = C.c_int64
+        L.vit_decode_punctured_dev.argtypes = [vp, vp, C.c_uint32, C.c_int64, C.POINTER(PunctProfile), C.c_uint8, vp]
+        L.vit_decode_punctured_varlen_dev.argtypes = [vp, C.c_uint64, vp, C.c_uint64, vp, C.c_int64, C.c_uint32, vp,
+                                                      C.c_uint32, C.c_uint8, vp]
         _lib = L
     return _lib
 
@@ -248,6 +266,59 @@ def dabplus_superframes_dev(d_symbols_u8, d_work, d_rs_out, d_ret, RSDims, nsf, 
     _check(lib().vit_dabplus_superframes_dev(C.c_void_p(d_symbols_u8.data_ptr()), C.c_void_p(d_work.data_ptr()),
                                              C.c_void_p(d_rs_out.data_ptr()), C.c_void_p(d_ret.data_ptr()),
                                              RSDims, nsf, _stream_ptr(stream)), "vit_dabplus_superframes_dev")
+
+
+def punct_profile(segments):
+    """(steps, keep) pairs -> PunctProfile.  keep: an int (bit 4*(k mod 8) + j = symbol j of the segment's k-th step
+    is transmitted) or a string of at most 32 '0'/'1' characters in the standard's v0...v31 order (keep = sum v_i << i).
+    Validity (segment count, zero-step segments, the step sum) is the library's to judge: punctured_length()."""
+    segments = list(segments)
+    if len(segments) > PUNCT_MAX_SEGS:
+        raise ValueError("at most %d segments" % PUNCT_MAX_SEGS)
+    p = PunctProfile()
+    p.nsegs = len(segments)
+    for k, (steps, keep) in enumerate(segments):
+        if isinstance(keep, str):
+            if not keep or len(keep) > 32 or set(keep) - {"0", "1"}:
+                raise ValueError("puncturing vector must be 1..32 characters '0'/'1': %r" % keep)
+            keep = sum(1 << i for i, v in enumerate(keep) if v == "1")
+        p.seg[k].steps = int(steps)
+        p.seg[k].keep = int(keep) & 0xFFFFFFFF
+    return p
+
+
+def punctured_length(profile, framebits):
+    """transmitted symbols of one frame under `profile`, or -1 (invalid, or steps != framebits + 6)"""
+    if not isinstance(profile, PunctProfile):
+        profile = punct_profile(profile)
+    return int(lib().vit_punctured_length(C.byref(profile), framebits))
+
+
+def decode_punctured_dev(d_punct, d_out, framebits, nframes, profile, erasure=128, stream=None):
+    """d_punct: torch uint8 CUDA tensor, frame f's transmitted symbols at f*punctured_length(profile, framebits)
+    (any alignment); profile: PunctProfile or (steps, keep) pairs; output as decode_batch_dev"""
+    if not isinstance(profile, PunctProfile):
+        profile = punct_profile(profile)
+    _check(lib().vit_decode_punctured_dev(C.c_void_p(d_punct.data_ptr()), C.c_void_p(d_out.data_ptr()), framebits, nframes,
+                                          C.byref(profile), int(erasure), _stream_ptr(stream)), "vit_decode_punctured_dev")
+
+
+def decode_punctured_varlen_dev(d_punct, d_out, d_desc, nframes, max_framebits, d_profiles, nprofiles, erasure=128,
+                                stream=None, sym_bytes=None, out_bytes=None):
+    """descriptors (DESC_DTYPE on the device): sym_offset = the frame's transmitted symbols in d_punct, reserved = its
+    profile's index in d_profiles (a device tensor of nprofiles PunctProfile images); checked against the buffer sizes
+    (default: the tensors' sizes) like decode_varlen_dev_checked"""
+    _check(lib().vit_decode_punctured_varlen_dev(
+        C.c_void_p(d_punct.data_ptr()), d_punct.numel() if sym_bytes is None else sym_bytes,
+        C.c_void_p(d_out.data_ptr()), d_out.numel() if out_bytes is None else out_bytes,
+        C.c_void_p(d_desc.data_ptr()), nframes, max_framebits, C.c_void_p(d_profiles.data_ptr()), nprofiles, int(erasure),
+        _stream_ptr(stream)), "vit_decode_punctured_varlen_dev")
+
+
+def profiles_bytes(profiles):
+    """host image of a profile table (PunctProfile or (steps, keep) pairs each) -> uint8 numpy array"""
+    return np.frombuffer(b"".join(bytes(p if isinstance(p, PunctProfile) else punct_profile(p)) for p in profiles),
+                         np.uint8).copy()
 
 
 def decode_stream_multi(d_symbols_u8, d_out, framebits, nframes, devices, chunk_frames, root_frames=-1, flags=0,

@@ -977,6 +977,80 @@ int vit_decode_varlen_dev_checked(const uint8_t* d_symbols_u8, uint64_t sym_byte
     return VIT_OK;
 }
 
+int64_t vit_punctured_length(const vit_punct_profile* p, uint32_t framebits) {
+    return vit_punct_length_host(p, framebits, nullptr, nullptr);
+}
+
+// Punctured input: the transmitted symbols are expanded into this thread's scratch buffer on the caller's current
+// device (the one the u32 path narrows into; vit_punct.hip), and the unchanged decoders read them from there.  The
+// buffer's reuse across the caller's streams is ordered by scratch_ev, as on the u32 path.
+int vit_decode_punctured_dev(const uint8_t* d_punct, uint8_t* d_decoded, uint32_t framebits, int64_t nframes,
+                             const vit_punct_profile* profile, uint8_t erasure, void* stream) {
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (!valid_framebits(framebits) || nframes < 0 || (nframes > 0 && framebits > 0 && !d_decoded)) {
+        set_err("vit_decode_punctured_dev: bad arguments (framebits=%u nframes=%lld)", framebits, (long long)nframes);
+        return VIT_ERR_ARG;
+    }
+    if (framebits == 0 || nframes == 0) return VIT_OK;
+    const int64_t P = vit_punctured_length(profile, framebits);
+    if (P < 0) {
+        set_err("vit_decode_punctured_dev: invalid puncturing profile, or its steps do not sum to framebits+6 = %u",
+                framebits + VIT_TAIL);
+        return VIT_ERR_ARG;
+    }
+    if (P > 0 && !d_punct) {  // (a profile that punctures everything reads no input)
+        set_err("vit_decode_punctured_dev: bad arguments (d_punct)");
+        return VIT_ERR_ARG;
+    }
+    const size_t nsym = (size_t)nframes * 4u * (framebits + VIT_TAIL);
+    int dev = -1;
+    HIPCHK(hipGetDevice(&dev));
+    int rc = ctx_prepare(dev);
+    if (rc != VIT_OK) return rc;
+    if ((rc = grow_dev(&t_ctx.d_sym8, &t_ctx.d8_cap, nsym)) != VIT_OK) return rc;
+    if (!t_ctx.scratch_ev) HIPCHK(hipEventCreateWithFlags(&t_ctx.scratch_ev, hipEventDisableTiming));
+    else HIPCHK(hipStreamWaitEvent((hipStream_t)stream, t_ctx.scratch_ev, 0));
+    hipError_t e = vit_launch_depunct(d_punct, (uint8_t*)t_ctx.d_sym8, framebits, nframes, profile, erasure, (hipStream_t)stream);
+    if (e != hipSuccess) { set_err("depuncture launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
+    rc = launch_decode(decode_mode(), (const uint8_t*)t_ctx.d_sym8, d_decoded, nullptr, framebits, framebits, nframes,
+                       (hipStream_t)stream);
+    if (rc != VIT_OK) return rc;
+    HIPCHK(hipEventRecord(t_ctx.scratch_ev, (hipStream_t)stream));
+    return VIT_OK;
+}
+
+int vit_decode_punctured_varlen_dev(const uint8_t* d_punct, uint64_t sym_bytes, uint8_t* d_decoded, uint64_t out_bytes,
+                                    const vit_frame_desc* d_desc, int64_t nframes, uint32_t max_framebits,
+                                    const vit_punct_profile* d_profiles, uint32_t nprofiles, uint8_t erasure, void* stream) {
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (!valid_framebits(max_framebits) || nframes < 0 ||
+        (nframes > 0 && (!d_punct || !d_decoded || !d_desc || (nprofiles > 0 && !d_profiles)))) {
+        set_err("vit_decode_punctured_varlen_dev: bad arguments");
+        return VIT_ERR_ARG;
+    }
+    if (nframes == 0 || max_framebits == 0) return VIT_OK;
+    // frame i's expanded symbols go to slot i of this thread's scratch buffer (no scan over the lengths), its
+    // internal descriptor to the thread's descriptor scratch (the checked path's copy); both on the caller's current
+    // device, their reuse ordered by scratch_ev.  The sort and the long-frame kernel keep their own scratch (vit_pk.hip).
+    const size_t slot = 4u * ((size_t)max_framebits + VIT_TAIL);
+    int dev = -1;
+    HIPCHK(hipGetDevice(&dev));
+    int rc = ctx_prepare(dev);
+    if (rc != VIT_OK) return rc;
+    if ((rc = grow_dev(&t_ctx.d_sym8, &t_ctx.d8_cap, (size_t)nframes * slot)) != VIT_OK) return rc;
+    if ((rc = grow_dev(&t_ctx.d_desc, &t_ctx.ddesc_cap, (size_t)nframes * sizeof(vit_frame_desc))) != VIT_OK) return rc;
+    if (!t_ctx.scratch_ev) HIPCHK(hipEventCreateWithFlags(&t_ctx.scratch_ev, hipEventDisableTiming));
+    else HIPCHK(hipStreamWaitEvent((hipStream_t)stream, t_ctx.scratch_ev, 0));
+    hipError_t e = vit_launch_depunct_varlen(d_punct, sym_bytes, out_bytes, d_desc, nframes, max_framebits, d_profiles, nprofiles,
+                                             erasure, (uint8_t*)t_ctx.d_sym8, (vit_frame_desc*)t_ctx.d_desc, (hipStream_t)stream);
+    if (e != hipSuccess) { set_err("depuncture launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
+    rc = launch_decode(decode_mode(), (const uint8_t*)t_ctx.d_sym8, d_decoded, (const vit_frame_desc*)t_ctx.d_desc, 0,
+                       max_framebits, nframes, (hipStream_t)stream);
+    if (rc != VIT_OK) return rc;
+    HIPCHK(hipEventRecord(t_ctx.scratch_ev, (hipStream_t)stream));
+    return VIT_OK;
+}
+
 void vit_sort_descs(vit_frame_desc* h_desc, int64_t nframes) {
     if (!h_desc || nframes <= 1) return;
     std::stable_sort(h_desc, h_desc + nframes,

@@ -66,6 +66,21 @@ hipError_t vit_check_descs_launch(const vit_frame_desc* d_desc, vit_frame_desc* 
 // u32 -> u8 narrowing (low byte), the reference ABI's symbol format to the device format.
 hipError_t vit_launch_pack(const uint32_t* d_sym32, uint8_t* d_sym8, int64_t nsym,
                            hipStream_t stream);
+// Depuncturing (vit_punct.hip).  Transmitted symbols of one frame under a HOST profile, or -1 (invalid profile, steps
+// not summing to framebits + 6); start/base (optional, VIT_PUNCT_MAX_SEGS entries) receive each segment's first step
+// and first transmitted byte.
+int64_t vit_punct_length_host(const vit_punct_profile* p, uint32_t framebits, uint32_t* start, uint32_t* base);
+// Uniform batch: frame f's transmitted bytes at d_punct + f*P, expanded into d_sym8 in the device format (frame f at
+// f*4*(framebits+6)).  hipErrorInvalidValue for a profile that vit_punct_length_host rejects.
+hipError_t vit_launch_depunct(const uint8_t* d_punct, uint8_t* d_sym8, uint32_t framebits, int64_t nframes,
+                              const vit_punct_profile* profile, uint8_t erasure, hipStream_t stream);
+// Variable-length batch with per-frame DEVICE profiles (desc[i].reserved = profile index): frame i is expanded into
+// d_slots + i*4*(max_framebits+6) and d_idesc[i] receives its internal descriptor - framebits 0xFFFFFFFF (skipped by
+// every decoder) for a descriptor that fails a check of vit_decode_punctured_varlen_dev.
+hipError_t vit_launch_depunct_varlen(const uint8_t* d_punct, uint64_t sym_bytes, uint64_t out_bytes, const vit_frame_desc* d_desc,
+                                     int64_t nframes, uint32_t max_framebits, const vit_punct_profile* d_profiles,
+                                     uint32_t nprofiles, uint8_t erasure, uint8_t* d_slots, vit_frame_desc* d_idesc,
+                                     hipStream_t stream);
 // RS(120,110) superframe check, one lane per column.
 // host_polls_ret (nsf == 1, rsdims <= 256): d_ret is host-visible and receives its value with system-scope release
 // semantics after the last output byte, so the host may spin on it instead of synchronising the stream.
