@@ -224,6 +224,55 @@ int vit_decode_punctured_varlen_dev(const uint8_t *d_punct, uint64_t sym_bytes, 
                                     uint32_t max_framebits, const vit_punct_profile *d_profiles,
                                     uint32_t nprofiles, uint8_t erasure, void *stream);
 
+/* After the decoder (EN 300 401 clauses 5.2.1 and 10, TS 102 563 clause 6).  Every convolutionally coded stream is
+ * scrambled before encoding, so a receiver undoes the energy dispersal on the decoded bytes first, then checks them.
+ * Built-in definitions:
+ *   energy dispersal PRBS  p_i = p_{i-9} XOR p_{i-5}, p_{-9} ... p_{-1} all 1 (x^9 + x^5 + 1, all-ones start); it
+ *                          starts 0000 0111 1011 1110 (bytes 0x07 0xBE) and has period 511.  It restarts at the first
+ *                          bit of every frame (the 768-bit FIC coding block, the 24 ms logical frame of an MSC
+ *                          sub-channel); decoded bit i of a frame (MSB first, the decoder's layout) is XORed with p_i;
+ *                          the padding bits of a partial last byte stay as they are.
+ *   FIB CRC                CRC-16, g(x) = x^16 + x^12 + x^5 + 1 (0x1021), register preset 0xFFFF, MSB first over a
+ *                          FIB's bytes 0..29; bytes 30..31 hold its ones' complement, MSB first (CRC-16/GENIBUS,
+ *                          check value 0xD64E).  A FIB passes when the recomputed value equals bytes 30..31.
+ *   DAB+ fire code         g(x) = (x^11 + 1)(x^5 + x^3 + x^2 + x + 1) = 0x782F, register 0, no final XOR: the
+ *                          remainder of a superframe's bytes 2..10 (MSB first) must equal bytes 0..1.  Checked on the
+ *                          descrambled bytes before RS: the receiver's superframe-sync test.
+ * Argument rules and errors as the other *_dev calls (VIT_ERR_NO_DEVICE first, VIT_ERR_ARG with vit_last_error(),
+ * everything enqueued on `stream` without synchronising, an empty batch returns VIT_OK and writes nothing).  Device
+ * pointers may have any alignment; no byte outside a frame's own bytes is read or written, so frames may share a
+ * dword.  The decode in the chains below uses the process's renormalise comparator (vit_set_renorm_ge). */
+/* Host only, needs no GPU: the PRBS as XOR bytes for one frame, (framebits+7)/8 bytes, padding bits 0.
+ * Returns the byte count, or -1 for odd framebits, framebits > 9216 or a NULL h_out. */
+int64_t vit_energy_dispersal_prbs(uint8_t *h_out, uint32_t framebits);
+/* In place, nframes frames of (framebits+7)/8 bytes back to back (the decoded-output layout); framebits even,
+ * <= 9216. */
+int vit_energy_dispersal_dev(uint8_t *d_bytes, uint32_t framebits, int64_t nframes, void *stream);
+/* In place, over the frames a DEVICE descriptor table names (out_offset, framebits; sym_offset and reserved are
+ * ignored).  A descriptor with odd framebits, framebits > 9216, or output bytes outside [0, out_bytes) is skipped
+ * (checked on the device); d_desc is not modified. */
+int vit_energy_dispersal_varlen_dev(uint8_t *d_bytes, uint64_t out_bytes, const vit_frame_desc *d_desc,
+                                    int64_t nframes, void *stream);
+/* nfibs consecutive 32-byte FIBs (already descrambled) -> d_ok[i] = 1 if FIB i's CRC holds, else 0.  d_fibs is only
+ * read. */
+int vit_fib_crc_dev(const uint8_t *d_fibs, int64_t nfibs, uint8_t *d_ok, void *stream);
+/* FIC chain: [depuncture ->] decode -> descramble -> FIB CRC; one kernel after the decode reads every decoded byte
+ * once, writes it back descrambled and writes the flags.
+ * framebits: a multiple of 256 in 256 ... 9216 (768 for the FIC coding block of modes I, II and IV).
+ * profile == NULL: d_in holds depunctured u8 symbols as for vit_decode_batch_dev.
+ * Otherwise: transmitted symbols as for vit_decode_punctured_dev (same scratch use).
+ * d_fibs receives the descrambled frames (nframes*framebits/8 bytes), d_fib_ok nframes*framebits/256 flags. */
+int vit_decode_fic_dev(const uint8_t *d_in, uint8_t *d_fibs, uint8_t *d_fib_ok, uint32_t framebits,
+                       int64_t nframes, const vit_punct_profile *profile, uint8_t erasure, void *stream);
+/* DAB+ chain: [depuncture ->] decode 5*nsf frames of 192*RSDims bits into d_work -> descramble each frame -> fire-code
+ * flag per superframe (d_fire_ok may be NULL) -> batched RScheckSuperframe as vit_rs_batch_dev.  RSDims 1 ... 48.
+ * profile NULL / non-NULL as for vit_decode_fic_dev.  (vit_dabplus_superframes_dev does not descramble: it is kept
+ * for unscrambled input.) */
+int vit_dabplus_punctured_superframes_dev(const uint8_t *d_in, const vit_punct_profile *profile,
+                                          uint8_t erasure, uint8_t *d_work, uint8_t *d_rs_out,
+                                          int32_t *d_ret, uint8_t *d_fire_ok, uint32_t RSDims,
+                                          int64_t nsf, void *stream);
+
 /* Kernel selection (the analogue of the reference's dispatcher, setupdll.cpp:195-270):
  *   0 = auto: launches of up to 2048 frames (they cannot fill the chip) take the latency kernel - one
  *       frame per wavefront, ~20 us per FIC frame -, larger ones the packed throughput kernel;

@@ -25,6 +25,8 @@ EXPORTS = [
     "vit_decode_batch_dev_u32", "vit_decode_varlen_dev", "vit_decode_varlen_dev_checked", "vit_pack_symbols_dev", "vit_sort_descs",
     "vit_decode_batch_host", "vit_rs_batch_dev", "vit_rs_batch_host", "vit_dabplus_superframes_dev",
     "vit_punctured_length", "vit_decode_punctured_dev", "vit_decode_punctured_varlen_dev",
+    "vit_energy_dispersal_prbs", "vit_energy_dispersal_dev", "vit_energy_dispersal_varlen_dev", "vit_fib_crc_dev",
+    "vit_decode_fic_dev", "vit_dabplus_punctured_superframes_dev",
     "vit_decode_stream_multi",
 ]
 MULTI_LOOPBACK = 0x1
@@ -105,6 +107,14 @@ def lib():
         L.vit_decode_punctured_dev.argtypes = [vp, vp, C.c_uint32, C.c_int64, C.POINTER(PunctProfile), C.c_uint8, vp]
         L.vit_decode_punctured_varlen_dev.argtypes = [vp, C.c_uint64, vp, C.c_uint64, vp, C.c_int64, C.c_uint32, vp,
                                                       C.c_uint32, C.c_uint8, vp]
+        L.vit_energy_dispersal_prbs.argtypes = [vp, C.c_uint32]
+        L.vit_energy_dispersal_prbs.restype = C.c_int64
+        L.vit_energy_dispersal_dev.argtypes = [vp, C.c_uint32, C.c_int64, vp]
+        L.vit_energy_dispersal_varlen_dev.argtypes = [vp, C.c_uint64, vp, C.c_int64, vp]
+        L.vit_fib_crc_dev.argtypes = [vp, C.c_int64, vp, vp]
+        L.vit_decode_fic_dev.argtypes = [vp, vp, vp, C.c_uint32, C.c_int64, C.POINTER(PunctProfile), C.c_uint8, vp]
+        L.vit_dabplus_punctured_superframes_dev.argtypes = [vp, C.POINTER(PunctProfile), C.c_uint8, vp, vp, vp, vp,
+                                                            C.c_uint32, C.c_int64, vp]
         _lib = L
     return _lib
 
@@ -319,6 +329,64 @@ def profiles_bytes(profiles):
     """host image of a profile table (PunctProfile or (steps, keep) pairs each) -> uint8 numpy array"""
     return np.frombuffer(b"".join(bytes(p if isinstance(p, PunctProfile) else punct_profile(p)) for p in profiles),
                          np.uint8).copy()
+
+
+def _ptr(t):
+    """device tensor -> its address, None -> NULL"""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _profile_ref(profile):
+    """None (depunctured input) or a PunctProfile / (steps, keep) pairs -> the argument of the chains below"""
+    if profile is None:
+        return None
+    return C.byref(profile if isinstance(profile, PunctProfile) else punct_profile(profile))
+
+
+def prbs_bytes(framebits):
+    """the energy dispersal PRBS as the XOR bytes of one frame ((framebits+7)//8, padding bits 0) -> uint8 numpy array;
+    ValueError for odd framebits or framebits > 9216 (host only, needs no GPU)"""
+    out = np.zeros(max((int(framebits) + 7) // 8, 1), np.uint8)
+    n = lib().vit_energy_dispersal_prbs(out.ctypes.data_as(C.c_void_p), int(framebits) & 0xFFFFFFFF)
+    if n < 0:
+        raise ValueError("framebits must be even and <= %d: %r" % (MAX_FRAMEBITS, framebits))
+    return out[:n]
+
+
+def energy_dispersal_dev(d_bytes, framebits, nframes, stream=None):
+    """in place: nframes frames of (framebits+7)//8 bytes back to back (torch uint8 CUDA tensor, any alignment)"""
+    _check(lib().vit_energy_dispersal_dev(_ptr(d_bytes), framebits, nframes, _stream_ptr(stream)), "vit_energy_dispersal_dev")
+
+
+def energy_dispersal_varlen_dev(d_bytes, d_desc, nframes, stream=None, out_bytes=None):
+    """in place over the frames of a descriptor table (DESC_DTYPE on the device: out_offset, framebits); descriptors
+    reaching outside out_bytes (default: d_bytes's size) or with invalid framebits are skipped"""
+    _check(lib().vit_energy_dispersal_varlen_dev(_ptr(d_bytes), d_bytes.numel() if out_bytes is None else out_bytes,
+                                                 _ptr(d_desc), nframes, _stream_ptr(stream)),
+           "vit_energy_dispersal_varlen_dev")
+
+
+def fib_crc_dev(d_fibs, nfibs, d_ok, stream=None):
+    """nfibs 32-byte FIBs (descrambled) -> d_ok[i] = 1 if FIB i's CRC-16 holds, else 0"""
+    _check(lib().vit_fib_crc_dev(_ptr(d_fibs), nfibs, _ptr(d_ok), _stream_ptr(stream)), "vit_fib_crc_dev")
+
+
+def decode_fic_dev(d_in, d_fibs, d_fib_ok, framebits, nframes, profile=None, erasure=128, stream=None):
+    """FIC chain: [depuncture ->] decode -> descramble -> FIB CRC.  profile None: d_in holds depunctured u8 symbols;
+    otherwise a PunctProfile or (steps, keep) pairs and d_in the transmitted symbols.  d_fibs receives the descrambled
+    frames, d_fib_ok nframes*framebits/256 flags."""
+    _check(lib().vit_decode_fic_dev(_ptr(d_in), _ptr(d_fibs), _ptr(d_fib_ok), framebits, nframes, _profile_ref(profile),
+                                    int(erasure), _stream_ptr(stream)), "vit_decode_fic_dev")
+
+
+def dabplus_punctured_superframes_dev(d_in, profile, d_work, d_rs_out, d_ret, RSDims, nsf, d_fire_ok=None, erasure=128,
+                                      stream=None):
+    """DAB+ chain: [depuncture ->] decode 5*nsf frames of 192*RSDims bits into d_work -> descramble -> fire-code flag
+    per superframe (d_fire_ok, optional) -> batched RScheckSuperframe into d_rs_out / d_ret.  profile as for
+    decode_fic_dev."""
+    _check(lib().vit_dabplus_punctured_superframes_dev(_ptr(d_in), _profile_ref(profile), int(erasure), _ptr(d_work),
+                                                       _ptr(d_rs_out), _ptr(d_ret), _ptr(d_fire_ok), RSDims, nsf,
+                                                       _stream_ptr(stream)), "vit_dabplus_punctured_superframes_dev")
 
 
 def decode_stream_multi(d_symbols_u8, d_out, framebits, nframes, devices, chunk_frames, root_frames=-1, flags=0,

@@ -984,22 +984,25 @@ int64_t vit_punctured_length(const vit_punct_profile* p, uint32_t framebits) {
 // Punctured input: the transmitted symbols are expanded into this thread's scratch buffer on the caller's current
 // device (the one the u32 path narrows into; vit_punct.hip), and the unchanged decoders read them from there.  The
 // buffer's reuse across the caller's streams is ordered by scratch_ev, as on the u32 path.
-int vit_decode_punctured_dev(const uint8_t* d_punct, uint8_t* d_decoded, uint32_t framebits, int64_t nframes,
-                             const vit_punct_profile* profile, uint8_t erasure, void* stream) {
-    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
-    if (!valid_framebits(framebits) || nframes < 0 || (nframes > 0 && framebits > 0 && !d_decoded)) {
-        set_err("vit_decode_punctured_dev: bad arguments (framebits=%u nframes=%lld)", framebits, (long long)nframes);
-        return VIT_ERR_ARG;
+// Shared by vit_decode_punctured_dev and the chains after the decoder: profile == NULL decodes depunctured u8 symbols
+// directly (no expansion, no scratch).  The caller has checked framebits (> 0), nframes (> 0) and d_out; the profile
+// and d_in are checked here, before anything is launched.
+static int decode_maybe_punctured(const char* who, const uint8_t* d_in, uint8_t* d_out, uint32_t framebits, int64_t nframes,
+                                  const vit_punct_profile* profile, uint8_t erasure, hipStream_t stream) {
+    if (!profile) {
+        if (!d_in) {
+            set_err("%s: bad arguments (d_in)", who);
+            return VIT_ERR_ARG;
+        }
+        return launch_decode(decode_mode(), d_in, d_out, nullptr, framebits, framebits, nframes, stream);
     }
-    if (framebits == 0 || nframes == 0) return VIT_OK;
     const int64_t P = vit_punctured_length(profile, framebits);
     if (P < 0) {
-        set_err("vit_decode_punctured_dev: invalid puncturing profile, or its steps do not sum to framebits+6 = %u",
-                framebits + VIT_TAIL);
+        set_err("%s: invalid puncturing profile, or its steps do not sum to framebits+6 = %u", who, framebits + VIT_TAIL);
         return VIT_ERR_ARG;
     }
-    if (P > 0 && !d_punct) {  // (a profile that punctures everything reads no input)
-        set_err("vit_decode_punctured_dev: bad arguments (d_punct)");
+    if (P > 0 && !d_in) {  // (a profile that punctures everything reads no input)
+        set_err("%s: bad arguments (d_punct)", who);
         return VIT_ERR_ARG;
     }
     const size_t nsym = (size_t)nframes * 4u * (framebits + VIT_TAIL);
@@ -1009,14 +1012,30 @@ int vit_decode_punctured_dev(const uint8_t* d_punct, uint8_t* d_decoded, uint32_
     if (rc != VIT_OK) return rc;
     if ((rc = grow_dev(&t_ctx.d_sym8, &t_ctx.d8_cap, nsym)) != VIT_OK) return rc;
     if (!t_ctx.scratch_ev) HIPCHK(hipEventCreateWithFlags(&t_ctx.scratch_ev, hipEventDisableTiming));
-    else HIPCHK(hipStreamWaitEvent((hipStream_t)stream, t_ctx.scratch_ev, 0));
-    hipError_t e = vit_launch_depunct(d_punct, (uint8_t*)t_ctx.d_sym8, framebits, nframes, profile, erasure, (hipStream_t)stream);
+    else HIPCHK(hipStreamWaitEvent(stream, t_ctx.scratch_ev, 0));
+    hipError_t e = vit_launch_depunct(d_in, (uint8_t*)t_ctx.d_sym8, framebits, nframes, profile, erasure, stream);
     if (e != hipSuccess) { set_err("depuncture launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
-    rc = launch_decode(decode_mode(), (const uint8_t*)t_ctx.d_sym8, d_decoded, nullptr, framebits, framebits, nframes,
-                       (hipStream_t)stream);
+    rc = launch_decode(decode_mode(), (const uint8_t*)t_ctx.d_sym8, d_out, nullptr, framebits, framebits, nframes, stream);
     if (rc != VIT_OK) return rc;
-    HIPCHK(hipEventRecord(t_ctx.scratch_ev, (hipStream_t)stream));
+    HIPCHK(hipEventRecord(t_ctx.scratch_ev, stream));
     return VIT_OK;
+}
+
+int vit_decode_punctured_dev(const uint8_t* d_punct, uint8_t* d_decoded, uint32_t framebits, int64_t nframes,
+                             const vit_punct_profile* profile, uint8_t erasure, void* stream) {
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (!valid_framebits(framebits) || nframes < 0 || (nframes > 0 && framebits > 0 && !d_decoded)) {
+        set_err("vit_decode_punctured_dev: bad arguments (framebits=%u nframes=%lld)", framebits, (long long)nframes);
+        return VIT_ERR_ARG;
+    }
+    if (framebits == 0 || nframes == 0) return VIT_OK;
+    if (!profile) {  // (NULL means "not punctured" only to the chains after the decoder)
+        set_err("vit_decode_punctured_dev: invalid puncturing profile, or its steps do not sum to framebits+6 = %u",
+                framebits + VIT_TAIL);
+        return VIT_ERR_ARG;
+    }
+    return decode_maybe_punctured("vit_decode_punctured_dev", d_punct, d_decoded, framebits, nframes, profile, erasure,
+                                  (hipStream_t)stream);
 }
 
 int vit_decode_punctured_varlen_dev(const uint8_t* d_punct, uint64_t sym_bytes, uint8_t* d_decoded, uint64_t out_bytes,
@@ -1048,6 +1067,88 @@ int vit_decode_punctured_varlen_dev(const uint8_t* d_punct, uint64_t sym_bytes, 
                        max_framebits, nframes, (hipStream_t)stream);
     if (rc != VIT_OK) return rc;
     HIPCHK(hipEventRecord(t_ctx.scratch_ev, (hipStream_t)stream));
+    return VIT_OK;
+}
+
+// ---- after the decoder: energy dispersal, FIB CRC, DAB+ fire code (vit_dab.hip) ----------------------------------
+int64_t vit_energy_dispersal_prbs(uint8_t* h_out, uint32_t framebits) {
+    if (!valid_framebits(framebits) || !h_out) {
+        set_err("vit_energy_dispersal_prbs: bad arguments (framebits=%u)", framebits);
+        return -1;
+    }
+    return vit_prbs_bytes_host(h_out, framebits);
+}
+
+int vit_energy_dispersal_dev(uint8_t* d_bytes, uint32_t framebits, int64_t nframes, void* stream) {
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (!valid_framebits(framebits) || nframes < 0 || (nframes > 0 && framebits > 0 && !d_bytes)) {
+        set_err("vit_energy_dispersal_dev: bad arguments (framebits=%u nframes=%lld)", framebits, (long long)nframes);
+        return VIT_ERR_ARG;
+    }
+    hipError_t e = vit_launch_disperse(d_bytes, framebits, nframes, (hipStream_t)stream);
+    if (e != hipSuccess) { set_err("energy dispersal launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
+    return VIT_OK;
+}
+
+int vit_energy_dispersal_varlen_dev(uint8_t* d_bytes, uint64_t out_bytes, const vit_frame_desc* d_desc, int64_t nframes,
+                                    void* stream) {
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (nframes < 0 || (nframes > 0 && (!d_bytes || !d_desc))) {
+        set_err("vit_energy_dispersal_varlen_dev: bad arguments");
+        return VIT_ERR_ARG;
+    }
+    hipError_t e = vit_launch_disperse_varlen(d_bytes, out_bytes, d_desc, nframes, (hipStream_t)stream);
+    if (e != hipSuccess) { set_err("energy dispersal launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
+    return VIT_OK;
+}
+
+int vit_fib_crc_dev(const uint8_t* d_fibs, int64_t nfibs, uint8_t* d_ok, void* stream) {
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (nfibs < 0 || (nfibs > 0 && (!d_fibs || !d_ok))) {
+        set_err("vit_fib_crc_dev: bad arguments");
+        return VIT_ERR_ARG;
+    }
+    hipError_t e = vit_launch_fibs(const_cast<uint8_t*>(d_fibs), nfibs, 1, false, d_ok, (hipStream_t)stream);
+    if (e != hipSuccess) { set_err("FIB CRC launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
+    return VIT_OK;
+}
+
+int vit_decode_fic_dev(const uint8_t* d_in, uint8_t* d_fibs, uint8_t* d_fib_ok, uint32_t framebits, int64_t nframes,
+                       const vit_punct_profile* profile, uint8_t erasure, void* stream) {
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (framebits == 0 || framebits % 256u != 0 || framebits > VIT_MAX_FRAMEBITS || nframes < 0 ||
+        (nframes > 0 && (!d_fibs || !d_fib_ok))) {
+        set_err("vit_decode_fic_dev: bad arguments (framebits=%u, a multiple of 256 up to 9216; nframes=%lld)", framebits,
+                (long long)nframes);
+        return VIT_ERR_ARG;
+    }
+    if (nframes == 0) return VIT_OK;
+    int rc = decode_maybe_punctured("vit_decode_fic_dev", d_in, d_fibs, framebits, nframes, profile, erasure,
+                                    (hipStream_t)stream);
+    if (rc != VIT_OK) return rc;
+    const uint32_t fpf = framebits / 256u;
+    hipError_t e = vit_launch_fibs(d_fibs, nframes * fpf, fpf, true, d_fib_ok, (hipStream_t)stream);
+    if (e != hipSuccess) { set_err("FIB post-pass launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
+    return VIT_OK;
+}
+
+int vit_dabplus_punctured_superframes_dev(const uint8_t* d_in, const vit_punct_profile* profile, uint8_t erasure,
+                                          uint8_t* d_work, uint8_t* d_rs_out, int32_t* d_ret, uint8_t* d_fire_ok,
+                                          uint32_t RSDims, int64_t nsf, void* stream) {
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (RSDims == 0 || 192ull * RSDims > VIT_MAX_FRAMEBITS || nsf < 0 || (nsf > 0 && (!d_work || !d_rs_out || !d_ret))) {
+        set_err("vit_dabplus_punctured_superframes_dev: bad arguments (RSDims=%u, 1 ... 48; nsf=%lld)", RSDims,
+                (long long)nsf);
+        return VIT_ERR_ARG;
+    }
+    if (nsf == 0) return VIT_OK;
+    int rc = decode_maybe_punctured("vit_dabplus_punctured_superframes_dev", d_in, d_work, 192u * RSDims, 5 * nsf, profile,
+                                    erasure, (hipStream_t)stream);
+    if (rc != VIT_OK) return rc;
+    hipError_t e = vit_launch_dabplus_post(d_work, RSDims, nsf, d_fire_ok, (hipStream_t)stream);
+    if (e != hipSuccess) { set_err("DAB+ post-pass launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
+    e = rs_launch(d_work, d_rs_out, d_ret, RSDims, nsf, (hipStream_t)stream);
+    if (e != hipSuccess) { set_err("rs launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
     return VIT_OK;
 }
 

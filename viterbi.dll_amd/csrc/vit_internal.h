@@ -81,6 +81,22 @@ hipError_t vit_launch_depunct_varlen(const uint8_t* d_punct, uint64_t sym_bytes,
                                      int64_t nframes, uint32_t max_framebits, const vit_punct_profile* d_profiles,
                                      uint32_t nprofiles, uint8_t erasure, uint8_t* d_slots, vit_frame_desc* d_idesc,
                                      hipStream_t stream);
+// After the decoder (vit_dab.hip).  The energy dispersal PRBS of one frame, (framebits+7)/8 bytes, padding bits 0
+// (framebits even, <= 9216; the caller checks).
+int64_t vit_prbs_bytes_host(uint8_t* h_out, uint32_t framebits);
+// In place: nframes frames of (framebits+7)/8 bytes back to back XORed with the PRBS.
+hipError_t vit_launch_disperse(uint8_t* d_bytes, uint32_t framebits, int64_t nframes, hipStream_t stream);
+// In place over a descriptor table (out_offset, framebits); descriptors with odd framebits, framebits > 9216 or output
+// bytes outside [0, out_bytes) are skipped.
+hipError_t vit_launch_disperse_varlen(uint8_t* d_bytes, uint64_t out_bytes, const vit_frame_desc* d_desc, int64_t nframes,
+                                      hipStream_t stream);
+// nfibs 32-byte FIBs back to back, fibs_per_frame of them per frame: descrambled in place first if `descramble`
+// (d_fibs is only read otherwise), then d_ok[i] = 1 if FIB i's CRC-16 holds, else 0.
+hipError_t vit_launch_fibs(uint8_t* d_fibs, int64_t nfibs, uint32_t fibs_per_frame, bool descramble, uint8_t* d_ok,
+                           hipStream_t stream);
+// DAB+: 5*nsf frames of 24*rsdims bytes descrambled in place; d_fire_ok[s] (optional) = the fire code of superframe s
+// on its descrambled bytes 0..10.
+hipError_t vit_launch_dabplus_post(uint8_t* d_work, uint32_t rsdims, int64_t nsf, uint8_t* d_fire_ok, hipStream_t stream);
 // RS(120,110) superframe check, one lane per column.
 // host_polls_ret (nsf == 1, rsdims <= 256): d_ret is host-visible and receives its value with system-scope release
 // semantics after the last output byte, so the host may spin on it instead of synchronising the stream.
