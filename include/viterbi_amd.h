@@ -273,6 +273,52 @@ int vit_dabplus_punctured_superframes_dev(const uint8_t *d_in, const vit_punct_p
                                           int32_t *d_ret, uint8_t *d_fire_ok, uint32_t RSDims,
                                           int64_t nsf, void *stream);
 
+/* From the CIF stream: MSC time de-interleaving (EN 300 401 clause 12).  Every MSC sub-channel (DAB and DAB+ audio,
+ * data; not the FIC) is spread over 16 logical frames, so a CIF carries one sixteenth of each of 16 logical frames.
+ * Built-in definition:
+ *   F = {0, 8, 4, 12, 2, 10, 6, 14, 1, 9, 5, 13, 3, 11, 7, 15}     (F[k] = k with its 4 bits reversed)
+ *   transmitter:  bit i of a sub-channel in CIF r  =  bit i of its logical frame r - F[i mod 16]
+ *   these calls:  byte i of logical frame n of the call  =  ring row (first_row + n + F[i mod 16]) mod nrows,
+ *                 column col + i
+ * i counts the sub-channel's transmitted (punctured) symbols from its first one, one soft byte per symbol - the order
+ * vit_decode_punctured_dev reads.  Frame n needs rows n ... n+15 and is complete once they are in, so a receiver's first
+ * call may start at the row of the first CIF it received.  Only the 15 logical frames before that one, whose bytes began
+ * in CIFs it never received, are incomplete, and no call addresses them.
+ * Whole MSC at once: sub-channels start at whole CUs of 64 bits and 64 = 0 (mod 16), so in a row that starts at CU 0
+ * a sub-channel's i mod 16 equals its column mod 16.  One de-interleave over the whole MSC width (col = the row's
+ * CU 0) therefore de-interleaves every sub-channel at once; a sub-channel then starts at column 64*startCU of each
+ * de-interleaved frame.  (A start that is not a multiple of 16 columns breaks this.)
+ * The input is a ring of CIF rows on the device, so a streaming receiver never copies the 15-row overlap between
+ * calls.  The struct is a HOST struct, read during the call.
+ * Argument rules as the other *_dev calls: VIT_ERR_NO_DEVICE first; VIT_ERR_ARG (with vit_last_error()) for a NULL
+ * ring or d_base, first_row >= nrows, nframes + 15 > nrows (the call's rows must be distinct ring rows),
+ * col + ncols > row_bytes, or an invalid profile; an empty batch returns VIT_OK and writes nothing; everything is
+ * enqueued on `stream` without synchronising.
+ * Guarantees: the call reads no byte outside columns [col, col + ncols) of its nframes + 15 rows, so the front end may
+ * be writing other rows of the ring meanwhile (ordering between the two is the caller's, with streams and events).
+ * Pointers, col and row_bytes may have any alignment. */
+typedef struct vit_cif_ring {
+    const uint8_t *d_base;  /* device; row r at d_base + r * row_bytes */
+    uint64_t row_bytes;     /* row stride: one CIF in the caller's layout */
+    uint32_t nrows;         /* rows in the ring */
+    uint32_t first_row;     /* < nrows: the row of the call's frame 0 (its F = 0 bytes) */
+} vit_cif_ring;
+/* Frame n's ncols de-interleaved bytes to d_out + n*ncols (nothing else is written).  The whole-CIF recipe: one call
+ * over the whole MSC width, then vit_decode_punctured_varlen_dev with sym_offset = n*ncols + 64*startCU per
+ * sub-channel frame. */
+int vit_time_deinterleave_dev(const vit_cif_ring *ring, uint64_t col, uint32_t ncols, uint8_t *d_out,
+                              int64_t nframes, void *stream);
+/* One sub-channel, columns [col, col + P) with P = vit_punctured_length(profile, framebits), decoded over nframes
+ * consecutive logical frames; the de-interleave is fused into the depuncturing expansion.  Output and scratch use as
+ * vit_decode_punctured_dev; `profile` is required. */
+int vit_decode_punctured_ti_dev(const vit_cif_ring *ring, uint64_t col, uint8_t *d_decoded, uint32_t framebits,
+                                int64_t nframes, const vit_punct_profile *profile, uint8_t erasure, void *stream);
+/* The DAB+ chain of vit_dabplus_punctured_superframes_dev from the ring: 5*nsf logical frames (5*nsf + 15 rows).
+ * `profile` is required (no NULL form). */
+int vit_dabplus_ti_superframes_dev(const vit_cif_ring *ring, uint64_t col, const vit_punct_profile *profile,
+                                   uint8_t erasure, uint8_t *d_work, uint8_t *d_rs_out, int32_t *d_ret,
+                                   uint8_t *d_fire_ok, uint32_t RSDims, int64_t nsf, void *stream);
+
 /* Kernel selection (the analogue of the reference's dispatcher, setupdll.cpp:195-270):
  *   0 = auto: launches of up to 2048 frames (they cannot fill the chip) take the latency kernel - one
  *       frame per wavefront, ~20 us per FIC frame -, larger ones the packed throughput kernel;

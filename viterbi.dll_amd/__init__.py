@@ -27,6 +27,7 @@ EXPORTS = [
     "vit_punctured_length", "vit_decode_punctured_dev", "vit_decode_punctured_varlen_dev",
     "vit_energy_dispersal_prbs", "vit_energy_dispersal_dev", "vit_energy_dispersal_varlen_dev", "vit_fib_crc_dev",
     "vit_decode_fic_dev", "vit_dabplus_punctured_superframes_dev",
+    "vit_time_deinterleave_dev", "vit_decode_punctured_ti_dev", "vit_dabplus_ti_superframes_dev",
     "vit_decode_stream_multi",
 ]
 MULTI_LOOPBACK = 0x1
@@ -55,6 +56,11 @@ class PunctSeg(C.Structure):
 class PunctProfile(C.Structure):
     """vit_punct_profile of include/viterbi_amd.h (68 bytes; bytes(profile) is its device image)"""
     _fields_ = [("nsegs", C.c_uint32), ("seg", PunctSeg * PUNCT_MAX_SEGS)]
+
+
+class CifRing(C.Structure):
+    """vit_cif_ring of include/viterbi_amd.h: a ring of CIF rows on the device"""
+    _fields_ = [("d_base", C.c_void_p), ("row_bytes", C.c_uint64), ("nrows", C.c_uint32), ("first_row", C.c_uint32)]
 
 _lib = None
 
@@ -115,6 +121,10 @@ def lib():
         L.vit_decode_fic_dev.argtypes = [vp, vp, vp, C.c_uint32, C.c_int64, C.POINTER(PunctProfile), C.c_uint8, vp]
         L.vit_dabplus_punctured_superframes_dev.argtypes = [vp, C.POINTER(PunctProfile), C.c_uint8, vp, vp, vp, vp,
                                                             C.c_uint32, C.c_int64, vp]
+        pr, pp = C.POINTER(CifRing), C.POINTER(PunctProfile)
+        L.vit_time_deinterleave_dev.argtypes = [pr, C.c_uint64, C.c_uint32, vp, C.c_int64, vp]
+        L.vit_decode_punctured_ti_dev.argtypes = [pr, C.c_uint64, vp, C.c_uint32, C.c_int64, pp, C.c_uint8, vp]
+        L.vit_dabplus_ti_superframes_dev.argtypes = [pr, C.c_uint64, pp, C.c_uint8, vp, vp, vp, vp, C.c_uint32, C.c_int64, vp]
         _lib = L
     return _lib
 
@@ -387,6 +397,46 @@ def dabplus_punctured_superframes_dev(d_in, profile, d_work, d_rs_out, d_ret, RS
     _check(lib().vit_dabplus_punctured_superframes_dev(_ptr(d_in), _profile_ref(profile), int(erasure), _ptr(d_work),
                                                        _ptr(d_rs_out), _ptr(d_ret), _ptr(d_fire_ok), RSDims, nsf,
                                                        _stream_ptr(stream)), "vit_dabplus_punctured_superframes_dev")
+
+
+def cif_ring(d_ring, first_row):
+    """a C-contiguous 2-D uint8 CUDA tensor (nrows, row_bytes) of CIF rows + the row of the call's frame 0 -> CifRing"""
+    if d_ring.dim() != 2 or str(d_ring.dtype) != "torch.uint8" or not d_ring.is_contiguous() or not d_ring.is_cuda:
+        raise ValueError("the ring must be a C-contiguous 2-D uint8 CUDA tensor (nrows, row_bytes)")
+    r = CifRing()
+    r.d_base = d_ring.data_ptr()
+    r.row_bytes = d_ring.shape[1]
+    r.nrows = d_ring.shape[0]
+    r.first_row = int(first_row)
+    return r
+
+
+def time_deinterleave_dev(d_ring, first_row, col, ncols, d_out, nframes, stream=None):
+    """MSC time de-interleaving (include/viterbi_amd.h): frame n's ncols bytes, byte i from ring row
+    (first_row + n + F[i % 16]) % nrows, column col + i, to d_out[n*ncols:(n+1)*ncols]"""
+    _check(lib().vit_time_deinterleave_dev(C.byref(cif_ring(d_ring, first_row)), col, ncols, _ptr(d_out), nframes,
+                                           _stream_ptr(stream)), "vit_time_deinterleave_dev")
+
+
+def decode_punctured_ti_dev(d_ring, first_row, col, d_out, framebits, nframes, profile, erasure=128, stream=None):
+    """one sub-channel at columns [col, col + punctured_length(profile, framebits)) of the ring, decoded over nframes
+    logical frames (de-interleave fused into the depuncturing); output as decode_punctured_dev"""
+    if not isinstance(profile, PunctProfile):
+        profile = punct_profile(profile)
+    _check(lib().vit_decode_punctured_ti_dev(C.byref(cif_ring(d_ring, first_row)), col, _ptr(d_out), framebits, nframes,
+                                             C.byref(profile), int(erasure), _stream_ptr(stream)),
+           "vit_decode_punctured_ti_dev")
+
+
+def dabplus_ti_superframes_dev(d_ring, first_row, col, profile, d_work, d_rs_out, d_ret, RSDims, nsf, d_fire_ok=None,
+                               erasure=128, stream=None):
+    """the DAB+ chain of dabplus_punctured_superframes_dev from the ring: 5*nsf logical frames (5*nsf + 15 rows);
+    profile required"""
+    if not isinstance(profile, PunctProfile):
+        profile = punct_profile(profile)
+    _check(lib().vit_dabplus_ti_superframes_dev(C.byref(cif_ring(d_ring, first_row)), col, C.byref(profile), int(erasure),
+                                                _ptr(d_work), _ptr(d_rs_out), _ptr(d_ret), _ptr(d_fire_ok), RSDims, nsf,
+                                                _stream_ptr(stream)), "vit_dabplus_ti_superframes_dev")
 
 
 def decode_stream_multi(d_symbols_u8, d_out, framebits, nframes, devices, chunk_frames, root_frames=-1, flags=0,

@@ -981,14 +981,41 @@ int64_t vit_punctured_length(const vit_punct_profile* p, uint32_t framebits) {
     return vit_punct_length_host(p, framebits, nullptr, nullptr);
 }
 
+// The argument rules of a CIF ring (include/viterbi_amd.h, vit_cif_ring) for a call of nframes > 0 frames that reads
+// ncols columns from col: false (with the error text set) if one is broken.
+static bool check_ring(const char* who, const vit_cif_ring* ring, uint64_t col, uint64_t ncols, int64_t nframes) {
+    if (!ring || !ring->d_base) {
+        set_err("%s: bad arguments (NULL ring or d_base)", who);
+        return false;
+    }
+    if (ring->first_row >= ring->nrows) {
+        set_err("%s: bad arguments (first_row %u >= nrows %u)", who, ring->first_row, ring->nrows);
+        return false;
+    }
+    if ((uint64_t)nframes + 15u > ring->nrows) {
+        set_err("%s: bad arguments (%lld frames need %lld distinct rows, the ring has %u)", who, (long long)nframes,
+                (long long)nframes + 15, ring->nrows);
+        return false;
+    }
+    if (col > ring->row_bytes || ncols > ring->row_bytes - col) {
+        set_err("%s: bad arguments (columns [%llu, %llu + %llu) outside row_bytes %llu)", who, (unsigned long long)col,
+                (unsigned long long)col, (unsigned long long)ncols, (unsigned long long)ring->row_bytes);
+        return false;
+    }
+    return true;
+}
+
 // Punctured input: the transmitted symbols are expanded into this thread's scratch buffer on the caller's current
 // device (the one the u32 path narrows into; vit_punct.hip), and the unchanged decoders read them from there.  The
 // buffer's reuse across the caller's streams is ordered by scratch_ev, as on the u32 path.
 // Shared by vit_decode_punctured_dev and the chains after the decoder: profile == NULL decodes depunctured u8 symbols
 // directly (no expansion, no scratch).  The caller has checked framebits (> 0), nframes (> 0) and d_out; the profile
 // and d_in are checked here, before anything is launched.
+// ring != NULL (the *_ti_dev calls, profile required): the transmitted symbols come from columns [col, col + P) of a CIF
+// ring instead of d_in, and the expansion de-interleaves them (vit_ti.hip).
 static int decode_maybe_punctured(const char* who, const uint8_t* d_in, uint8_t* d_out, uint32_t framebits, int64_t nframes,
-                                  const vit_punct_profile* profile, uint8_t erasure, hipStream_t stream) {
+                                  const vit_punct_profile* profile, uint8_t erasure, hipStream_t stream,
+                                  const vit_cif_ring* ring = nullptr, uint64_t col = 0) {
     if (!profile) {
         if (!d_in) {
             set_err("%s: bad arguments (d_in)", who);
@@ -1001,7 +1028,9 @@ static int decode_maybe_punctured(const char* who, const uint8_t* d_in, uint8_t*
         set_err("%s: invalid puncturing profile, or its steps do not sum to framebits+6 = %u", who, framebits + VIT_TAIL);
         return VIT_ERR_ARG;
     }
-    if (P > 0 && !d_in) {  // (a profile that punctures everything reads no input)
+    if (ring) {
+        if (!check_ring(who, ring, col, (uint64_t)P, nframes)) return VIT_ERR_ARG;
+    } else if (P > 0 && !d_in) {  // (a profile that punctures everything reads no input)
         set_err("%s: bad arguments (d_punct)", who);
         return VIT_ERR_ARG;
     }
@@ -1013,7 +1042,8 @@ static int decode_maybe_punctured(const char* who, const uint8_t* d_in, uint8_t*
     if ((rc = grow_dev(&t_ctx.d_sym8, &t_ctx.d8_cap, nsym)) != VIT_OK) return rc;
     if (!t_ctx.scratch_ev) HIPCHK(hipEventCreateWithFlags(&t_ctx.scratch_ev, hipEventDisableTiming));
     else HIPCHK(hipStreamWaitEvent(stream, t_ctx.scratch_ev, 0));
-    hipError_t e = vit_launch_depunct(d_in, (uint8_t*)t_ctx.d_sym8, framebits, nframes, profile, erasure, stream);
+    hipError_t e = ring ? vit_launch_depunct_ti(*ring, col, (uint8_t*)t_ctx.d_sym8, framebits, nframes, profile, erasure, stream)
+                        : vit_launch_depunct(d_in, (uint8_t*)t_ctx.d_sym8, framebits, nframes, profile, erasure, stream);
     if (e != hipSuccess) { set_err("depuncture launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
     rc = launch_decode(decode_mode(), (const uint8_t*)t_ctx.d_sym8, d_out, nullptr, framebits, framebits, nframes, stream);
     if (rc != VIT_OK) return rc;
@@ -1132,24 +1162,82 @@ int vit_decode_fic_dev(const uint8_t* d_in, uint8_t* d_fibs, uint8_t* d_fib_ok, 
     return VIT_OK;
 }
 
-int vit_dabplus_punctured_superframes_dev(const uint8_t* d_in, const vit_punct_profile* profile, uint8_t erasure,
-                                          uint8_t* d_work, uint8_t* d_rs_out, int32_t* d_ret, uint8_t* d_fire_ok,
-                                          uint32_t RSDims, int64_t nsf, void* stream) {
+// The DAB+ chain of both entry points; from_ring: the *_ti_dev form, which reads `ring` (required, as the profile is)
+// instead of d_in.
+static int dabplus_chain(const char* who, const uint8_t* d_in, bool from_ring, const vit_cif_ring* ring, uint64_t col,
+                         const vit_punct_profile* profile, uint8_t erasure, uint8_t* d_work, uint8_t* d_rs_out, int32_t* d_ret,
+                         uint8_t* d_fire_ok, uint32_t RSDims, int64_t nsf, void* stream) {
     if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
     if (RSDims == 0 || 192ull * RSDims > VIT_MAX_FRAMEBITS || nsf < 0 || (nsf > 0 && (!d_work || !d_rs_out || !d_ret))) {
-        set_err("vit_dabplus_punctured_superframes_dev: bad arguments (RSDims=%u, 1 ... 48; nsf=%lld)", RSDims,
-                (long long)nsf);
+        set_err("%s: bad arguments (RSDims=%u, 1 ... 48; nsf=%lld)", who, RSDims, (long long)nsf);
         return VIT_ERR_ARG;
     }
     if (nsf == 0) return VIT_OK;
-    int rc = decode_maybe_punctured("vit_dabplus_punctured_superframes_dev", d_in, d_work, 192u * RSDims, 5 * nsf, profile,
-                                    erasure, (hipStream_t)stream);
+    if (from_ring && !ring) {
+        set_err("%s: bad arguments (NULL ring)", who);
+        return VIT_ERR_ARG;
+    }
+    if (from_ring && !profile) {
+        set_err("%s: a puncturing profile is required", who);
+        return VIT_ERR_ARG;
+    }
+    int rc = decode_maybe_punctured(who, d_in, d_work, 192u * RSDims, 5 * nsf, profile, erasure, (hipStream_t)stream, ring,
+                                    col);
     if (rc != VIT_OK) return rc;
     hipError_t e = vit_launch_dabplus_post(d_work, RSDims, nsf, d_fire_ok, (hipStream_t)stream);
     if (e != hipSuccess) { set_err("DAB+ post-pass launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
     e = rs_launch(d_work, d_rs_out, d_ret, RSDims, nsf, (hipStream_t)stream);
     if (e != hipSuccess) { set_err("rs launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
     return VIT_OK;
+}
+
+int vit_dabplus_punctured_superframes_dev(const uint8_t* d_in, const vit_punct_profile* profile, uint8_t erasure,
+                                          uint8_t* d_work, uint8_t* d_rs_out, int32_t* d_ret, uint8_t* d_fire_ok,
+                                          uint32_t RSDims, int64_t nsf, void* stream) {
+    return dabplus_chain("vit_dabplus_punctured_superframes_dev", d_in, false, nullptr, 0, profile, erasure, d_work, d_rs_out,
+                         d_ret, d_fire_ok, RSDims, nsf, stream);
+}
+
+// ---- from the CIF stream: MSC time de-interleaving (vit_ti.hip) ---------------------------------------------------
+int vit_time_deinterleave_dev(const vit_cif_ring* ring, uint64_t col, uint32_t ncols, uint8_t* d_out, int64_t nframes,
+                              void* stream) {
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (nframes < 0 || (nframes > 0 && ncols > 0 && !d_out)) {
+        set_err("vit_time_deinterleave_dev: bad arguments (nframes=%lld)", (long long)nframes);
+        return VIT_ERR_ARG;
+    }
+    if (nframes == 0) return VIT_OK;
+    if (!check_ring("vit_time_deinterleave_dev", ring, col, ncols, nframes)) return VIT_ERR_ARG;
+    hipError_t e = vit_launch_time_deinterleave(*ring, col, ncols, d_out, nframes, (hipStream_t)stream);
+    if (e != hipSuccess) { set_err("time de-interleave launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
+    return VIT_OK;
+}
+
+int vit_decode_punctured_ti_dev(const vit_cif_ring* ring, uint64_t col, uint8_t* d_decoded, uint32_t framebits,
+                                int64_t nframes, const vit_punct_profile* profile, uint8_t erasure, void* stream) {
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (!valid_framebits(framebits) || nframes < 0 || (nframes > 0 && framebits > 0 && !d_decoded)) {
+        set_err("vit_decode_punctured_ti_dev: bad arguments (framebits=%u nframes=%lld)", framebits, (long long)nframes);
+        return VIT_ERR_ARG;
+    }
+    if (framebits == 0 || nframes == 0) return VIT_OK;
+    if (!ring) {
+        set_err("vit_decode_punctured_ti_dev: bad arguments (NULL ring)");
+        return VIT_ERR_ARG;
+    }
+    if (!profile) {
+        set_err("vit_decode_punctured_ti_dev: a puncturing profile is required");
+        return VIT_ERR_ARG;
+    }
+    return decode_maybe_punctured("vit_decode_punctured_ti_dev", nullptr, d_decoded, framebits, nframes, profile, erasure,
+                                  (hipStream_t)stream, ring, col);
+}
+
+int vit_dabplus_ti_superframes_dev(const vit_cif_ring* ring, uint64_t col, const vit_punct_profile* profile, uint8_t erasure,
+                                   uint8_t* d_work, uint8_t* d_rs_out, int32_t* d_ret, uint8_t* d_fire_ok, uint32_t RSDims,
+                                   int64_t nsf, void* stream) {
+    return dabplus_chain("vit_dabplus_ti_superframes_dev", nullptr, true, ring, col, profile, erasure, d_work, d_rs_out, d_ret,
+                         d_fire_ok, RSDims, nsf, stream);
 }
 
 void vit_sort_descs(vit_frame_desc* h_desc, int64_t nframes) {

@@ -81,6 +81,14 @@ hipError_t vit_launch_depunct_varlen(const uint8_t* d_punct, uint64_t sym_bytes,
                                      int64_t nframes, uint32_t max_framebits, const vit_punct_profile* d_profiles,
                                      uint32_t nprofiles, uint8_t erasure, uint8_t* d_slots, vit_frame_desc* d_idesc,
                                      hipStream_t stream);
+// MSC time de-interleaving (vit_ti.hip); the caller has checked the ring (include/viterbi_amd.h, vit_cif_ring: the
+// call's nframes + 15 rows distinct, its columns inside row_bytes).  Standalone: frame n's ncols bytes to d_out + n*ncols.
+hipError_t vit_launch_time_deinterleave(const vit_cif_ring& ring, uint64_t col, uint32_t ncols, uint8_t* d_out,
+                                        int64_t nframes, hipStream_t stream);
+// Fused with the expansion: as vit_launch_depunct, frame n's transmitted symbols read from the ring at columns
+// [col, col + P).
+hipError_t vit_launch_depunct_ti(const vit_cif_ring& ring, uint64_t col, uint8_t* d_sym8, uint32_t framebits, int64_t nframes,
+                                 const vit_punct_profile* profile, uint8_t erasure, hipStream_t stream);
 // After the decoder (vit_dab.hip).  The energy dispersal PRBS of one frame, (framebits+7)/8 bytes, padding bits 0
 // (framebits even, <= 9216; the caller checks).
 int64_t vit_prbs_bytes_host(uint8_t* h_out, uint32_t framebits);

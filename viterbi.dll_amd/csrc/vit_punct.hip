@@ -18,50 +18,13 @@
 // per lane at a time leaves the pass latency-bound.  Variable-length batch: one workgroup per frame, each lane
 // computes its steps directly (a table would cost as much as the frame).
 #include "vit_internal.h"
+#include "vit_punct_dev.h"
 
 namespace {
 
 typedef uint32_t u32;
 typedef uint64_t u64;
 constexpr u32 TPB = 256;
-
-// Segment table of one profile: first step and first transmitted byte of every segment.  The uniform call computes it
-// on the host and passes it by value; the varlen kernel builds it per frame from the caller's device profile.
-struct SegTab {
-    u32 nsegs;
-    u32 start[VIT_PUNCT_MAX_SEGS];
-    u32 base[VIT_PUNCT_MAX_SEGS];
-    u32 keep[VIT_PUNCT_MAX_SEGS];
-};
-
-// v_perm_b32 selector that expands the packed transmitted bytes of a step with keep nibble `nib`: byte j takes packed
-// byte popc(nib & ((1 << j) - 1)) if symbol j is transmitted, else selector 4 = byte 0 of the erasure word (src0)
-__device__ __forceinline__ u32 expand_sel(u32 nib) {
-    u32 sel = 0, r = 0;
-#pragma unroll
-    for (u32 j = 0; j < 4; j++) {
-        const u32 bit = (nib >> j) & 1u;
-        sel |= (bit ? r : 4u) << (8u * j);
-        r += bit;
-    }
-    return sel;
-}
-
-// Segment lookup of frame-local step t: first transmitted byte and keep nibble
-__device__ __forceinline__ void locate(u32 t, const SegTab& tab, u32& off, u32& nib) {
-    u32 s0 = tab.start[0], b0 = tab.base[0], keep = tab.keep[0];
-#pragma unroll
-    for (u32 k = 1; k < VIT_PUNCT_MAX_SEGS; k++) {  // segments start in increasing order: the last one at or below t
-        if (k < tab.nsegs && t >= tab.start[k]) {
-            s0 = tab.start[k];
-            b0 = tab.base[k];
-            keep = tab.keep[k];
-        }
-    }
-    const u32 k = t - s0, ph = 4u * (k & 7u);
-    off = b0 + (k >> 3) * __builtin_popcount(keep) + __builtin_popcount(keep & ((1u << ph) - 1u));
-    nib = (keep >> ph) & 15u;
-}
 
 // The step's transmitted bytes, packed from byte 0 (off + popc(nib) <= P).  `in` = the frame's first transmitted byte.
 __device__ __forceinline__ u32 gather(const uint8_t* __restrict__ in, u32 P, u32 off, u32 nib) {
