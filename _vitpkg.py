@@ -30,3 +30,15 @@ def load_oracle():
     sys.modules[name] = mod
     spec.loader.exec_module(mod)
     return mod
+
+
+def load_ref():
+    """TEST INFRASTRUCTURE ONLY -- oracle/ref.py: the build of the reference's own decoders under oracle/_ref."""
+    name = "vit_ref_py"
+    if name in sys.modules:
+        return sys.modules[name]
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "oracle", "ref.py"))
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules[name] = mod
+    spec.loader.exec_module(mod)
+    return mod

@@ -7,17 +7,16 @@
  * cpu_baseline leg may load it, and only as the checker / the timed CPU
  * baseline.  The product path (viterbi.dll_amd/csrc) never links or calls it.
  *
- * Pinning status: the reference cannot be compiled in this image without
- * writing stand-ins for <windows.h>/<psapi.h> and restating const.asm (MASM),
- * so there is no oracle/_ref build, and the reference ships no golden vectors
- * of its own.  The oracle is pinned by the known-answer vectors recorded in
- * SURVEY.md section 8c (outputs of the compiled reference taken during the
- * survey: the 16-byte decoder prefix for framebits 288/768/6912, GF table
- * samples, two RScheckSuperframe behaviours) -- see tests/test_oracle_kat.py.
- * Beyond those vectors: PARITY UNPINNED (the survey's three full-length
- * FNV-1a digests could not be reproduced and are carried as a tripwire only);
- * tests/golden/ holds regression vectors made by this oracle, not reference
- * outputs.
+ * Pinning status: oracle/ref.py builds the reference's own deconvolve.cpp and
+ * rschecksf.cpp (C decoders, -D_VIT_NO_ASM_) with this repository's harness
+ * into oracle/_ref/, once as they are and once with RENORMALIZE_THRESHOLD 149
+ * (the MASM decoders' `>= 150`).  tests/test_ref_parity.py compares this
+ * oracle with both builds byte for byte, and with their committed results
+ * (tests/golden/reference_*.npy) where no reference checkout exists.  Not
+ * pinned: the assembled MASM decoders, the GF tables of dllmain.cpp (the
+ * harness builds its own).  tests/golden/golden.json holds vectors made by
+ * this oracle that the reference builds reproduce.  The older known-answer
+ * vectors of SURVEY.md section 8c stay in tests/test_oracle_kat.py.
  */
 #ifndef VIT_ORACLE_H
 #define VIT_ORACLE_H

@@ -1,16 +1,15 @@
 """Generates tests/golden/golden.json: regression vectors for the hot path.
 
-PROVENANCE: produced by THIS repo's oracle (oracle/vit_oracle.c), not by the reference --
-the reference cannot be built or run under this project's rules (it needs stand-ins for
-<windows.h>/<psapi.h> and MASM data).  The oracle itself is pinned by SURVEY 8c's KATs
-(tests/test_oracle_kat.py).  Inputs AND expected outputs are stored (inputs zlib-compressed + base64, plus
-their FNV-1a-64), so that the GPU suite can compare the HIP path with the committed bytes without loading
-the oracle at all.
+PROVENANCE: produced by THIS repo's oracle (oracle/vit_oracle.c).  The reference's own C decoders and RS checker
+(oracle/_ref, built by oracle/ref.py) reproduce every out_hex (RENORMALIZE_THRESHOLD 150), out_ge_hex (149), RS ret and
+RS out_hex in it: tests/test_ref_parity.py::test_reference_reproduces_golden_json.  Inputs AND expected outputs are stored
+(inputs zlib-compressed + base64, plus their FNV-1a-64), so that the GPU suite can compare the HIP path with the committed
+bytes without loading the oracle at all.
 
 Decode cases carry TWO expected outputs: `out_hex` for the `> 150` renormalise comparator (the reference's
 C decoders, deconvolve.cpp:407-412) and `out_ge_hex` for `>= 150` (its MASM decoders, decon_avx2.asm:94-118);
 on soft-decision input they are equal, the hard-decision cases are picked so that they DIFFER.  The ge
-outputs come from the oracle's restatement of asm text that cannot be assembled here (parity unpinned).
+outputs are those of the reference's C arithmetic with the MASM comparator; the assembled asm text itself is not pinned.
 """
 import base64
 import json
@@ -44,7 +43,7 @@ def make_sym(fb, kind, seed):
     raise ValueError(kind)
 
 
-g = {"provenance": "oracle/vit_oracle.c (own restatement); see make_golden.py", "decode": [], "rs": []}
+g = {"provenance": "oracle/vit_oracle.c (own restatement); reproduced in full by the reference's own C decoders and RS checker (oracle/_ref), tests/test_ref_parity.py; see make_golden.py", "decode": [], "rs": []}
 cases = [(768, "uniform", KAT), (288, "uniform", KAT), (768, "noisy", 11), (1536, "noisy", 12), (96, "uniform", 13),
          (8, "uniform", 14), (3072, "noisy", 15), (2304, "uniform", 16),
          # round 3: the longest DAB sub-channel frame, the ABI's maximum, a partial last byte, the shortest frame

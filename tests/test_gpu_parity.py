@@ -183,7 +183,7 @@ def test_renorm_ge_mode(V, O, torch_cuda, kernel, framebits, n):
     """vit_set_renorm_ge(1): the `>= 150` renormalise test of the reference's MASM decoders (decon_avx2.asm:94-118,
     the shipped Rel_asm configuration) against the oracle's ge mode; mode 0 (`> 150`, deconvolve.cpp:407-412, Rel_cpp)
     against the gt oracle on the SAME frames -- hard-decision input, where the two modes really differ (asserted).
-    The oracle's ge mode is restated from the asm text, which cannot be assembled here: parity unpinned."""
+    The oracle's ge mode is pinned to the reference's C decoders built with RENORMALIZE_THRESHOLD 149 (tests/test_ref_parity.py)."""
     sym = _hard_families(O, framebits, n, seed=framebits)
     want_gt = O.decode_batch(framebits, sym, nthreads=8)
     want_ge = O.decode_batch(framebits, sym, nthreads=8, ge=True)
