@@ -6,6 +6,11 @@ Decoder: per even framebits 2 ... 9216 the FNV-1a-64 of the output for a soft an
 RENORMALIZE_THRESHOLD 150 (`> 150`, the C decoders as they are) and 149 (`>= 150`, the MASM decoders' comparator), plus
 the digests of the inputs.  Every C variant this CPU runs (at 9216 bits: the 256-bit ones, see oracle/ref/harness.cpp) must produce the same bytes before anything is written.
 RS: per seeded superframe the return value, the digest of the sentinel-initialised output, the digest of the input.
+RS paths (reference_rs_paths.npy): the same four values for the syndrome-directed tables of tests/rsdirect.py
+(pinned_tables(): 64 columns of every class on their own, the first-failure, wide and export tables).
+
+Arguments select the parts to (re)write - decoder, rs, rs_paths - default all; reference_provenance.json is updated
+for the parts written.
 """
 import datetime
 import json
@@ -20,39 +25,64 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
 import _vitpkg  # noqa: E402
 import reffix  # noqa: E402
+import rsdirect  # noqa: E402
+
+PARTS = set(sys.argv[1:]) or {"decoder", "rs", "rs_paths"}
+assert PARTS <= {"decoder", "rs", "rs_paths"}, PARTS
 
 R = _vitpkg.load_ref()
 assert R.build(), "oracle/_ref is missing and there is no reference checkout to build it from"
 variants = R.variants()
 assert "sse2_lut32" in variants and len(variants) >= 4, variants
 
-soft, hard = reffix.decoder_inputs()
-tab = np.zeros((len(reffix.LENGTHS), len(reffix.COLS)), np.uint64)
-tab[:, 0], tab[:, 1] = reffix.fnv1a64_rows(soft), reffix.fnv1a64_rows(hard)
-for col, fam, ge in ((2, soft, False), (3, soft, True), (4, hard, False), (5, hard, True)):
-    outs = []
-    for fb, sym in zip(reffix.LENGTHS, fam):
-        got = [R.decode_batch(fb, sym, variant=v, ge=ge, nthreads=1)[0] for v in R.variants(fb)]
-        assert all(np.array_equal(got[0], g) for g in got[1:]), ("the reference's variants disagree", fb, ge)
-        outs.append(got[0])
-    tab[:, col] = reffix.fnv1a64_rows(outs)
-np.save(reffix.DECODER_NPY, tab)
+if "decoder" in PARTS:
+    soft, hard = reffix.decoder_inputs()
+    tab = np.zeros((len(reffix.LENGTHS), len(reffix.COLS)), np.uint64)
+    tab[:, 0], tab[:, 1] = reffix.fnv1a64_rows(soft), reffix.fnv1a64_rows(hard)
+    for col, fam, ge in ((2, soft, False), (3, soft, True), (4, hard, False), (5, hard, True)):
+        outs = []
+        for fb, sym in zip(reffix.LENGTHS, fam):
+            got = [R.decode_batch(fb, sym, variant=v, ge=ge, nthreads=1)[0] for v in R.variants(fb)]
+            assert all(np.array_equal(got[0], g) for g in got[1:]), ("the reference's variants disagree", fb, ge)
+            outs.append(got[0])
+        tab[:, col] = reffix.fnv1a64_rows(outs)
+    np.save(reffix.DECODER_NPY, tab)
 
-rows = []
-for rsdims in reffix.RS_DIMS:
-    p, _ = reffix.rs_superframes(rsdims)
-    ret, out = R.rs_check_batch(p, rsdims, np.full((p.shape[0], 110 * rsdims), reffix.RS_SENTINEL, np.uint8))
-    for s in range(p.shape[0]):
-        rows.append((rsdims, int(ret[s]) & reffix.M64, reffix.fnv1a64(out[s]), reffix.fnv1a64(p[s])))
-np.save(reffix.RS_NPY, np.array(rows, np.uint64))
+if "rs" in PARTS:
+    rows = []
+    for rsdims in reffix.RS_DIMS:
+        p, _ = reffix.rs_superframes(rsdims)
+        ret, out = R.rs_check_batch(p, rsdims, np.full((p.shape[0], 110 * rsdims), reffix.RS_SENTINEL, np.uint8))
+        for s in range(p.shape[0]):
+            rows.append((rsdims, int(ret[s]) & reffix.M64, reffix.fnv1a64(out[s]), reffix.fnv1a64(p[s])))
+    np.save(reffix.RS_NPY, np.array(rows, np.uint64))
+
+if "rs_paths" in PARTS:
+    C = rsdirect.classes()
+    ret_of = {label: R.rs_decode_words(k.words)[0] for label, k in C.items()}
+    paths_counts = rsdirect.non_vacuity(ret_of)
+    assert paths_counts["random_accepted"] >= 130, paths_counts  # of rsdirect.N_RANDOM columns: room above the tests' floor of 100
+    paths = rsdirect.pinned_rows(R.rs_check_batch)
+    np.save(rsdirect.RS_PATHS_NPY, paths)
+    assert os.path.getsize(rsdirect.RS_PATHS_NPY) < os.path.getsize(os.path.join(HERE, "golden.json"))
 
 info = R.build_info()
+prov = {}
+if PARTS != {"decoder", "rs", "rs_paths"}:
+    with open(reffix.PROVENANCE_JSON) as f:
+        prov = json.load(f)
+if PARTS & {"decoder", "rs"}:
+    prov.update({"what": "outputs of the reference's own deconvolve.cpp / rschecksf.cpp (C decoders, -D_VIT_NO_ASM_), "
+                         "built by oracle/ref.py with this repository's harness and stand-in headers",
+                 "reference_tag": R.REFERENCE_TAG, "compiler": info.get("compiler"), "flags": info.get("flags"),
+                 "thresholds": {"gt": 150, "ge": 149}, "variants_agreeing": variants,
+                 "date": datetime.date.today().isoformat(),
+                 "not_pinned": "the assembled MASM decoders; the GF tables of dllmain.cpp (the harness builds its own)"})
+if "rs_paths" in PARTS:
+    prov["rs_paths"] = {"what": "reference_rs_paths.npy: rschecksf.cpp on the syndrome-directed tables of tests/rsdirect.py",
+                        "reference_tag": R.REFERENCE_TAG, "compiler": info.get("compiler"), "date": datetime.date.today().isoformat(),
+                        "superframes": int(paths.shape[0]), "reference_counts": paths_counts,
+                        "class_digests": rsdirect.class_digests()}
 with open(reffix.PROVENANCE_JSON, "w") as f:
-    json.dump({"what": "outputs of the reference's own deconvolve.cpp / rschecksf.cpp (C decoders, -D_VIT_NO_ASM_), "
-                       "built by oracle/ref.py with this repository's harness and stand-in headers",
-               "reference_tag": R.REFERENCE_TAG, "compiler": info.get("compiler"), "flags": info.get("flags"),
-               "thresholds": {"gt": 150, "ge": 149}, "variants_agreeing": variants,
-               "date": datetime.date.today().isoformat(),
-               "not_pinned": "the assembled MASM decoders; the GF tables of dllmain.cpp (the harness builds its own)"},
-              f, indent=1)
-print("wrote", reffix.DECODER_NPY, tab.shape, "and", reffix.RS_NPY, len(rows), "superframes; variants", variants)
+    json.dump(prov, f, indent=1)
+print("wrote", sorted(PARTS), "variants", variants)

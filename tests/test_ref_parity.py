@@ -18,6 +18,7 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import _vitpkg  # noqa: E402
 import reffix  # noqa: E402
+import rsdirect  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -222,6 +223,12 @@ def test_reference_build_reproduces_its_committed_fixtures(R):
         row = tab[reffix.LENGTHS.index(fb)]
         got = [reffix.fnv1a64(R.decode_batch(fb, x, ge=ge)[0]) for x in (s, h) for ge in (False, True)]
         assert got == [int(v) for v in row[2:]], fb
+    rs = np.load(reffix.RS_NPY)
+    rows = [(rsdims, int(r) & reffix.M64, reffix.fnv1a64(o), reffix.fnv1a64(p))
+            for rsdims in reffix.RS_DIMS for P in [reffix.rs_superframes(rsdims)[0]]
+            for p, r, o in zip(P, *R.rs_check_batch(P, rsdims, np.full((P.shape[0], 110 * rsdims), reffix.RS_SENTINEL, np.uint8)))]
+    assert np.array_equal(np.array(rows, np.uint64), rs)
+    assert np.array_equal(rsdirect.pinned_rows(R.rs_check_batch), np.load(rsdirect.RS_PATHS_NPY))  # the syndrome-directed tables
 
 
 def test_oracle_reproduces_the_reference_fixtures(O):
@@ -255,5 +262,12 @@ def test_oracle_reproduces_the_reference_fixtures(O):
             row += 1
     rets = np.ascontiguousarray(rs[:, 1]).view(np.int64)
     assert (rets == 0).any() and (rets > 0).any() and (rets == -1).any()
+    # the syndrome-directed tables (tests/rsdirect.py): every return value, output digest and input digest
+    paths = np.load(rsdirect.RS_PATHS_NPY)
+    got = rsdirect.pinned_rows(O.rs_check_batch)
+    assert got.shape == paths.shape and np.array_equal(got[:, 3], paths[:, 3]), "RS path generator drifted"
+    assert np.array_equal(got, paths), np.flatnonzero((got != paths).any(axis=1))[:8]
+    prets = np.ascontiguousarray(paths[:, 1]).view(np.int64)
+    assert (paths[:, 0] == 1).sum() >= 64 * 48 and (prets[paths[:, 0] == 1] == 6).sum() >= 64  # degree-6 locators, accepted
     with open(reffix.PROVENANCE_JSON) as f:
         assert json.load(f)["reference_tag"] == "2024_10_08"

@@ -153,8 +153,12 @@ __device__ __forceinline__ uint32_t mod255(uint32_t x) { return (x * 0x1010102u)
 __device__ __forceinline__ uint32_t mod510(uint32_t x) { return x < x - NN ? x : x - NN; }  // x < 510 (x - 255 wraps below 255)
 
 // Chien search over i = 1..255 (rschecksf.cpp:299-320) in the reference's own form - the logs b[j] advance by j, the sum
-// is over alpha_to[b[j]] - for the rare wave that holds a locator above degree 5 (never correctable, but its roots are
-// counted).  Roots go to the column's parity rows like chien_wave's.  Lanes with need == false find nothing.
+// is over alpha_to[b[j]] - for the rare wave that holds a locator above degree 5.  Such a column is beyond the code's five
+// errors, but the reference accepts it whenever the locator splits into deg_lambda distinct roots (only
+// deg_lambda == count is checked): e.g. syndromes (0,0,0,0,0,s5..s9) end Berlekamp-Massey in a degree-6 locator without an
+// x^5 term, and one with six roots returns 6 and is patched by Forney like any other (tests/rsdirect.py builds them:
+// deg6_ok, short_6).  Every heavy lane of such a wave comes here, the degree-3..5 ones too.  Roots go to the column's
+// parity rows like chien_wave's (up to ten: rows 110..119).  Lanes with need == false find nothing.
 __device__ __forceinline__ int chien_log(const uint32_t (&lam)[NROOTS + 1], bool need, int deg_lambda, uint8_t* col,
                                          uint32_t stride, const uint8_t* __restrict__ ato) {
     uint32_t b[NROOTS + 1], live[NROOTS + 1];
