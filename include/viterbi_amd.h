@@ -319,6 +319,68 @@ int vit_dabplus_ti_superframes_dev(const vit_cif_ring *ring, uint64_t col, const
                                    uint8_t erasure, uint8_t *d_work, uint8_t *d_rs_out, int32_t *d_ret,
                                    uint8_t *d_fire_ok, uint32_t RSDims, int64_t nsf, void *stream);
 
+/* From the FFT: differential demodulation, frequency de-interleaving, QPSK demapping and quantisation of whole
+ * transmission frames (EN 300 401 clauses 14.5 - 14.7 seen from the receiver) - the step between an FFT on the device and
+ * vit_decode_fic_dev / the ring of the *_ti_dev calls.
+ * Input: the FFT outputs of whole frames, interleaved (re, im) float32, bin 0 = DC, in the order an FFT leaves them
+ * (carrier k < 0 at bin nfft + k).  Symbol l of frame t starts at complex element t*frame_stride + l*sym_stride (strides
+ * in complex elements, sym_stride >= nfft; the null symbol is the caller's to skip, which is what frame_stride is for).
+ * Symbol 0 of a frame is the phase reference symbol, symbols 1 ... nsyms-1 are data.  d_fft must be 16-byte aligned and
+ * both strides even (rocFFT output is).
+ * The shape of a frame is a HOST struct, read during the call; no table of transmission modes is compiled in. */
+typedef struct vit_ofdm_shape {
+    uint32_t nfft;      /* FFT length; power of two, 64 ... 8192 */
+    uint32_t ncarriers; /* K: QPSK symbols per OFDM symbol, 1 ... nfft; an OFDM symbol carries 2K bits */
+    uint32_t nsyms;     /* OFDM symbols per frame in d_fft, phase reference included (mode I: 76); > fic_syms */
+    uint32_t fic_syms;  /* the first fic_syms data symbols go to d_fic (mode I: 3) */
+    uint32_t cifs;      /* CIFs per frame (mode I: 4), >= 1; (nsyms - 1 - fic_syms) must be a multiple of it */
+} vit_ofdm_shape;
+/* mode I {2048,1536,76,3,4}, II {512,384,76,3,1}, III {256,192,153,8,1}, IV {1024,768,76,3,2} */
+/* Frequency de-interleaving is a caller-supplied DEVICE table d_bins[K]: QPSK symbol n of an OFDM symbol is carried by
+ * FFT bin d_bins[n].  The table is only read on the device, so it is checked there: its entries must be < nfft and
+ * distinct (a carrier bears one QPSK symbol).  For a table that breaks this the bytes of the carriers involved are
+ * unspecified, but nothing outside the rows of d_fft is read and nothing outside the call's own output bytes is written.
+ * The standard's table, a built-in definition like the PRBS and F (EN 300 401 clause 14.6):
+ * Host only, needs no GPU.  P(0) = 0, P(i) = (13*P(i-1) + nfft/4 - 1) mod nfft for i = 1 ... nfft-1; the values with
+ * nfft/8 <= P(i) <= 7*nfft/8 and P(i) != nfft/2, in the order they occur, are d_0 ... d_{K-1}, K = 3*nfft/4; QPSK
+ * symbol n travels on carrier k = d_n - nfft/2, i.e. FFT bin k mod nfft.  Writes K bins to h_bins and returns K,
+ * or -1 for nfft not in {256, 512, 1024, 2048} or a NULL pointer. */
+int64_t vit_freq_interleave_bins(uint32_t nfft, uint16_t *h_bins);
+/* Per data symbol l = 1 ... nsyms-1 of frame t and per n = 0 ... K-1, with a = z[t, l, d_bins[n]] and
+ * b = z[t, l-1, d_bins[n]], every operation an IEEE binary32 operation rounded to nearest-even, in exactly this order,
+ * never contracted into an FMA:
+ *   re  = fl(fl(a.re*b.re) + fl(a.im*b.im))          y = a * conj(b): pi/4-DQPSK leaves y on a diagonal,
+ *   im  = fl(fl(a.im*b.re) - fl(a.re*b.im))          re(y) > 0 <=> bit n = 0, im(y) > 0 <=> bit n+K = 0
+ *   nrm = fl(|re| + |im|)
+ *   if not (2^-64 <= nrm <= FLT_MAX):   out[n] = out[n+K] = 128        (no signal, NaN, Inf: erasures)
+ *   else  s = fl(gain / nrm)
+ *         out[n]   = clamp(128 - rint(fl(re*s)), 0, 255)
+ *         out[n+K] = clamp(128 - rint(fl(im*s)), 0, 255)               rint: ties to even
+ * gain: a host float, finite, 0 < gain <= 65536; an ideal constellation point gives 128 -/+ gain/2, so 254 uses the whole
+ * byte range there.  Normalising per carrier by |re| + |im| needs no reduction, so the result is defined bit for bit; the
+ * lower bound on nrm makes a muted carrier an erasure and keeps the result independent of how denormals are handled.
+ * Where the 2K bytes `out` of data symbol s = l-1 of frame t go:
+ *   s < fic_syms:  d_fic + (t*fic_syms + s) * 2K.  In modes I, II and IV a frame's fic_syms*2K bytes are whole blocks of
+ *                  2304 transmitted symbols: the input of vit_decode_fic_dev(..., 768, ..., &fic_profile, ...).
+ *   otherwise:     with m = s - fic_syms and per = (nsyms-1-fic_syms)/cifs, CIF c = m / per of the frame: ring row
+ *                  (first_row + t*cifs + c) mod nrows, columns col + (m mod per)*2K ...  With the rows of mode I
+ *                  (per*2K = 55296) that is the ring of the *_ti_dev calls, and first_row advances by nframes*cifs from
+ *                  call to call.
+ * This call is the ring's WRITER: it writes through ring->d_base (the struct keeps its `const` for the readers).
+ * d_fic may be NULL: the FIC symbols are not demapped.  ring may be NULL: the MSC symbols are not demapped and their rows
+ * of d_fft not read.
+ * Argument rules as the other *_dev calls: VIT_ERR_NO_DEVICE first; VIT_ERR_ARG (with vit_last_error()) for a NULL
+ * d_fft / d_bins / shape, both destinations NULL, a misaligned d_fft or an odd stride, sym_stride < nfft, an invalid shape
+ * or gain, nframes < 0, a ring with a NULL d_base, first_row >= nrows, nframes*cifs > nrows (the call's rows must be
+ * distinct), col + per*2K > row_bytes; an empty batch returns VIT_OK and writes nothing; everything is enqueued on
+ * `stream` without synchronising.
+ * Guarantees: no byte is written outside the bytes named above (d_fic, the ring, col and row_bytes may have any
+ * alignment); no bin that d_bins does not name influences any output (guard bins and DC may hold NaN); ring rows other
+ * than the call's nframes*cifs rows - the 15-row overlap of a streaming ring among them - are never touched. */
+int vit_ofdm_demap_dev(const float *d_fft, uint64_t sym_stride, uint64_t frame_stride, const uint16_t *d_bins,
+                       const vit_ofdm_shape *shape, float gain, int64_t nframes, uint8_t *d_fic,
+                       const vit_cif_ring *ring, uint64_t col, void *stream);
+
 /* Kernel selection (the analogue of the reference's dispatcher, setupdll.cpp:195-270):
  *   0 = auto: launches of up to 2048 frames (they cannot fill the chip) take the latency kernel - one
  *       frame per wavefront, ~20 us per FIC frame -, larger ones the packed throughput kernel;

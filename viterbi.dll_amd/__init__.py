@@ -28,6 +28,7 @@ EXPORTS = [
     "vit_energy_dispersal_prbs", "vit_energy_dispersal_dev", "vit_energy_dispersal_varlen_dev", "vit_fib_crc_dev",
     "vit_decode_fic_dev", "vit_dabplus_punctured_superframes_dev",
     "vit_time_deinterleave_dev", "vit_decode_punctured_ti_dev", "vit_dabplus_ti_superframes_dev",
+    "vit_freq_interleave_bins", "vit_ofdm_demap_dev",
     "vit_decode_stream_multi",
 ]
 MULTI_LOOPBACK = 0x1
@@ -61,6 +62,16 @@ class PunctProfile(C.Structure):
 class CifRing(C.Structure):
     """vit_cif_ring of include/viterbi_amd.h: a ring of CIF rows on the device"""
     _fields_ = [("d_base", C.c_void_p), ("row_bytes", C.c_uint64), ("nrows", C.c_uint32), ("first_row", C.c_uint32)]
+
+
+class OfdmShape(C.Structure):
+    """vit_ofdm_shape of include/viterbi_amd.h: OfdmShape(nfft, ncarriers, nsyms, fic_syms, cifs)"""
+    _fields_ = [("nfft", C.c_uint32), ("ncarriers", C.c_uint32), ("nsyms", C.c_uint32), ("fic_syms", C.c_uint32),
+                ("cifs", C.c_uint32)]
+
+
+# the four transmission modes of EN 300 401 as shapes (examples: the library compiles in no table of modes)
+OFDM_MODES = {1: (2048, 1536, 76, 3, 4), 2: (512, 384, 76, 3, 1), 3: (256, 192, 153, 8, 1), 4: (1024, 768, 76, 3, 2)}
 
 _lib = None
 
@@ -125,6 +136,10 @@ def lib():
         L.vit_time_deinterleave_dev.argtypes = [pr, C.c_uint64, C.c_uint32, vp, C.c_int64, vp]
         L.vit_decode_punctured_ti_dev.argtypes = [pr, C.c_uint64, vp, C.c_uint32, C.c_int64, pp, C.c_uint8, vp]
         L.vit_dabplus_ti_superframes_dev.argtypes = [pr, C.c_uint64, pp, C.c_uint8, vp, vp, vp, vp, C.c_uint32, C.c_int64, vp]
+        L.vit_freq_interleave_bins.argtypes = [C.c_uint32, vp]
+        L.vit_freq_interleave_bins.restype = C.c_int64
+        L.vit_ofdm_demap_dev.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.POINTER(OfdmShape), C.c_float, C.c_int64, vp, pr,
+                                         C.c_uint64, vp]
         _lib = L
     return _lib
 
@@ -437,6 +452,39 @@ def dabplus_ti_superframes_dev(d_ring, first_row, col, profile, d_work, d_rs_out
     _check(lib().vit_dabplus_ti_superframes_dev(C.byref(cif_ring(d_ring, first_row)), col, C.byref(profile), int(erasure),
                                                 _ptr(d_work), _ptr(d_rs_out), _ptr(d_ret), _ptr(d_fire_ok), RSDims, nsf,
                                                 _stream_ptr(stream)), "vit_dabplus_ti_superframes_dev")
+
+
+def freq_interleave_bins(nfft):
+    """the standard's frequency interleaving as FFT bins (include/viterbi_amd.h): QPSK symbol n of an OFDM symbol travels
+    in bin result[n]; 3*nfft/4 entries -> uint16 numpy array; ValueError for nfft not in 256, 512, 1024, 2048 (host only,
+    needs no GPU)"""
+    out = np.zeros(8192, np.uint16)
+    n = lib().vit_freq_interleave_bins(int(nfft) & 0xFFFFFFFF, _np(out))
+    if n < 0:
+        raise ValueError("nfft must be 256, 512, 1024 or 2048: %r" % (nfft,))
+    return out[:n].copy()
+
+
+def ofdm_demap_dev(d_fft, shape, d_bins, gain, nframes, d_fic=None, d_ring=None, first_row=0, col=0, sym_stride=None,
+                   frame_stride=None, stream=None):
+    """From the FFT (include/viterbi_amd.h): d_fft a complex64 or (re, im)-interleaved float32 CUDA tensor of nframes
+    frames; shape an OfdmShape or its 5 numbers; d_bins a uint16 CUDA tensor of K FFT bins (torch has no uint16
+    arithmetic: build it with freq_interleave_bins and torch.from_numpy(bins.view(np.int16)).cuda(), any 2-byte dtype
+    is taken); d_fic receives the FIC symbols' soft bytes and the rows of d_ring (as cif_ring) the CIFs, either may be
+    None.  Strides count complex elements and default to nfft and nsyms*sym_stride."""
+    if not isinstance(shape, OfdmShape):
+        shape = OfdmShape(*[int(v) for v in shape])
+    if not d_fft.is_cuda or str(d_fft.dtype) not in ("torch.complex64", "torch.float32"):
+        raise ValueError("d_fft must be a complex64 or float32 CUDA tensor")
+    if not d_bins.is_cuda or d_bins.element_size() != 2:
+        raise ValueError("d_bins must be a CUDA tensor of 2-byte elements (uint16 bins)")
+    if sym_stride is None:
+        sym_stride = shape.nfft
+    if frame_stride is None:
+        frame_stride = shape.nsyms * sym_stride
+    ring = None if d_ring is None else C.byref(cif_ring(d_ring, first_row))
+    _check(lib().vit_ofdm_demap_dev(_ptr(d_fft), sym_stride, frame_stride, _ptr(d_bins), C.byref(shape), float(gain), nframes,
+                                    _ptr(d_fic), ring, col, _stream_ptr(stream)), "vit_ofdm_demap_dev")
 
 
 def decode_stream_multi(d_symbols_u8, d_out, framebits, nframes, devices, chunk_frames, root_frames=-1, flags=0,

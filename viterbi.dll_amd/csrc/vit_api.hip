@@ -1240,6 +1240,70 @@ int vit_dabplus_ti_superframes_dev(const vit_cif_ring* ring, uint64_t col, const
                          d_fire_ok, RSDims, nsf, stream);
 }
 
+// ---- from the FFT: differential demodulation, frequency de-interleaving, demapping (vit_ofdm.hip) ------------------
+int64_t vit_freq_interleave_bins(uint32_t nfft, uint16_t* h_bins) {
+    const int64_t n = vit_freq_bins_host(nfft, h_bins);
+    if (n < 0) set_err("vit_freq_interleave_bins: bad arguments (nfft=%u, one of 256, 512, 1024, 2048)", nfft);
+    return n;
+}
+
+int vit_ofdm_demap_dev(const float* d_fft, uint64_t sym_stride, uint64_t frame_stride, const uint16_t* d_bins,
+                       const vit_ofdm_shape* shape, float gain, int64_t nframes, uint8_t* d_fic, const vit_cif_ring* ring,
+                       uint64_t col, void* stream) {
+    const char* who = "vit_ofdm_demap_dev";
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (!d_fft || !d_bins || !shape || nframes < 0) {
+        set_err("%s: bad arguments (NULL d_fft, d_bins or shape, or nframes=%lld < 0)", who, (long long)nframes);
+        return VIT_ERR_ARG;
+    }
+    if (!d_fic && !ring) {
+        set_err("%s: bad arguments (d_fic and ring both NULL)", who);
+        return VIT_ERR_ARG;
+    }
+    const vit_ofdm_shape& sh = *shape;
+    if (sh.nfft < 64u || sh.nfft > 8192u || (sh.nfft & (sh.nfft - 1u)) != 0 || sh.ncarriers == 0 || sh.ncarriers > sh.nfft ||
+        sh.nsyms <= sh.fic_syms || sh.cifs == 0 || (sh.nsyms - 1u - sh.fic_syms) % sh.cifs != 0) {
+        set_err("%s: bad arguments (shape {nfft=%u ncarriers=%u nsyms=%u fic_syms=%u cifs=%u})", who, sh.nfft, sh.ncarriers,
+                sh.nsyms, sh.fic_syms, sh.cifs);
+        return VIT_ERR_ARG;
+    }
+    if (!(gain > 0.0f && gain <= 65536.0f)) {  // false for NaN
+        set_err("%s: bad arguments (gain %g, 0 < gain <= 65536)", who, (double)gain);
+        return VIT_ERR_ARG;
+    }
+    if (((uintptr_t)d_fft & 15u) != 0 || (sym_stride & 1u) != 0 || (frame_stride & 1u) != 0 || sym_stride < sh.nfft) {
+        set_err("%s: bad arguments (d_fft must be 16-byte aligned, sym_stride %llu and frame_stride %llu even, sym_stride >= "
+                "nfft)", who, (unsigned long long)sym_stride, (unsigned long long)frame_stride);
+        return VIT_ERR_ARG;
+    }
+    if (ring) {
+        const uint64_t per_bytes = (uint64_t)((sh.nsyms - 1u - sh.fic_syms) / sh.cifs) * 2u * sh.ncarriers;
+        if (!ring->d_base) {
+            set_err("%s: bad arguments (NULL d_base)", who);
+            return VIT_ERR_ARG;
+        }
+        if (ring->first_row >= ring->nrows) {
+            set_err("%s: bad arguments (first_row %u >= nrows %u)", who, ring->first_row, ring->nrows);
+            return VIT_ERR_ARG;
+        }
+        if ((uint64_t)nframes > ring->nrows / sh.cifs) {
+            set_err("%s: bad arguments (%lld frames of %u CIFs need distinct rows, the ring has %u)", who, (long long)nframes,
+                    sh.cifs, ring->nrows);
+            return VIT_ERR_ARG;
+        }
+        if (col > ring->row_bytes || per_bytes > ring->row_bytes - col) {
+            set_err("%s: bad arguments (columns [%llu, %llu + %llu) outside row_bytes %llu)", who, (unsigned long long)col,
+                    (unsigned long long)col, (unsigned long long)per_bytes, (unsigned long long)ring->row_bytes);
+            return VIT_ERR_ARG;
+        }
+    }
+    if (nframes == 0) return VIT_OK;
+    hipError_t e = vit_launch_ofdm_demap(d_fft, sym_stride, frame_stride, d_bins, sh, gain, nframes, d_fic, ring, col,
+                                         (hipStream_t)stream);
+    if (e != hipSuccess) { set_err("OFDM demap launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
+    return VIT_OK;
+}
+
 void vit_sort_descs(vit_frame_desc* h_desc, int64_t nframes) {
     if (!h_desc || nframes <= 1) return;
     std::stable_sort(h_desc, h_desc + nframes,

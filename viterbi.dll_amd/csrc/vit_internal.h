@@ -89,6 +89,14 @@ hipError_t vit_launch_time_deinterleave(const vit_cif_ring& ring, uint64_t col, 
 // [col, col + P).
 hipError_t vit_launch_depunct_ti(const vit_cif_ring& ring, uint64_t col, uint8_t* d_sym8, uint32_t framebits, int64_t nframes,
                                  const vit_punct_profile* profile, uint8_t erasure, hipStream_t stream);
+// From the FFT (vit_ofdm.hip).  The standard's frequency interleaving as FFT bins (include/viterbi_amd.h,
+// vit_freq_interleave_bins): K = 3*nfft/4 bins to h_bins, or -1.
+int64_t vit_freq_bins_host(uint32_t nfft, uint16_t* h_bins);
+// Demaps nframes transmission frames; the caller has checked every argument rule of vit_ofdm_demap_dev.  d_fic / ring may
+// be NULL (those symbols are skipped).
+hipError_t vit_launch_ofdm_demap(const float* d_fft, uint64_t sym_stride, uint64_t frame_stride, const uint16_t* d_bins,
+                                 const vit_ofdm_shape& shape, float gain, int64_t nframes, uint8_t* d_fic,
+                                 const vit_cif_ring* ring, uint64_t col, hipStream_t stream);
 // After the decoder (vit_dab.hip).  The energy dispersal PRBS of one frame, (framebits+7)/8 bytes, padding bits 0
 // (framebits even, <= 9216; the caller checks).
 int64_t vit_prbs_bytes_host(uint8_t* h_out, uint32_t framebits);

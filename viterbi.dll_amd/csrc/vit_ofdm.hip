@@ -1,0 +1,236 @@
+// vit_ofdm.hip -- from the FFT to soft bytes (include/viterbi_amd.h, "From the FFT"): differential demodulation,
+// frequency de-interleaving, QPSK demapping and quantisation of whole transmission frames, the FIC's symbols to d_fic
+// and the MSC's to the ring of CIF rows that vit_ti.hip reads.
+//
+// The result is defined bit for bit, so every float operation below is a single IEEE binary32 operation: this file is
+// compiled with contraction off (the pragma; the rest of the library keeps the compiler's default), the arithmetic is
+// written with plain operators, and `/` is the compiler's correctly rounded expansion.
+//
+// One workgroup owns one frame and a run of consecutive data symbols.  A lane owns fixed 16-byte chunks (two bins) of a
+// row, in BIN order: row loads are coalesced dwordx4 loads, the previous symbol's values stay in the lane's registers (a
+// row is read once per run, plus one row at the run's start), and each chunk of the next row is loaded as soon as the
+// chunk of the previous row it replaces has been used: two rows of registers, at most 64 VGPRs, 8 workgroups per CU.  At its start the workgroup inverts d_bins into LDS (bin -> n, 0xFFFF for a bin no carrier uses)
+// and every lane keeps a mask of its chunks that carry anything; a chunk whose two bins are unused is never loaded, so the guard
+// band and DC cost no traffic and may hold anything.  The two soft bytes of a carrier go to positions n and n + K of
+// a 2K-byte LDS tile and the tile leaves as 16-byte stores of any alignment; two tiles, so one barrier per symbol.
+// A table entry >= nfft is ignored and of a repeated entry one n wins: the tile bytes nobody owns keep the erasure
+// value the tiles start with.
+#pragma clang fp contract(off)
+#include <cfloat>
+
+#include "vit_internal.h"
+
+namespace {
+
+typedef uint32_t u32;
+typedef uint64_t u64;
+constexpr u32 UNUSED = 0xFFFFu;  // K <= 8192, so no n reaches it
+constexpr u32 RUN_MAX = 25;      // data symbols per workgroup at most: one extra row read per run is then <= 4 %
+
+struct OfdmArgs {
+    const float4* fft;         // two carriers per element
+    u64 sym_stride2, frame_stride2;  // in float4 elements
+    const uint16_t* bins;
+    u32 nfft, K, fic_syms, cifs, per;
+    u32 lo, hi;      // the data symbols [lo, hi) of every frame are demapped
+    u32 run, runs;   // data symbols per workgroup, workgroups per frame
+    float gain;
+    uint8_t* fic;
+    uint8_t* ring;
+    u64 row_bytes, nrows, first_row, col;
+};
+
+// the two soft bytes of one carrier (low byte: bit n, next byte: bit n + K) from a = z[l], b = z[l-1]
+__device__ __forceinline__ u32 soft_pair(float ar, float ai, float br, float bi, float gain) {
+    const float re = ar * br + ai * bi;
+    const float im = ai * br - ar * bi;
+    const float nrm = __builtin_fabsf(re) + __builtin_fabsf(im);
+    u32 q = 0x8080u;
+    if (nrm >= 0x1p-64f && nrm <= FLT_MAX) {  // false for NaN
+        const float s = gain / nrm;
+        const float q0 = __builtin_fminf(__builtin_fmaxf(128.0f - __builtin_rintf(re * s), 0.0f), 255.0f);
+        const float q1 = __builtin_fminf(__builtin_fmaxf(128.0f - __builtin_rintf(im * s), 0.0f), 255.0f);
+        q = (u32)q0 | (u32)q1 << 8;
+    }
+    return q;
+}
+
+template <u32 TPB, u32 CPL>
+struct Row {
+    float4 v[CPL];
+};
+
+// Chunk j of a lane is float4 element threadIdx.x + j*TPB of a row, addressed as a uniform base plus the lane's 32-bit
+// byte offset; `used` bit j: the chunk has a carrier (the others are never loaded).
+template <u32 TPB>
+__device__ __forceinline__ float4 load_chunk(const float4* row, u32 j, u32 lane_off) {
+    return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(row + j * TPB) + lane_off);
+}
+
+template <u32 TPB, u32 CPL>
+__device__ __forceinline__ void load_row(const float4* row, u32 lane_off, u32 used, Row<TPB, CPL>& r) {
+#pragma unroll
+    for (u32 j = 0; j < CPL; j++) {
+        r.v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (used >> j & 1u) r.v[j] = load_chunk<TPB>(row, j, lane_off);
+    }
+}
+
+// One data symbol: a = its own row, b = the row before.  Writes the symbol's soft bytes to `tile`; a chunk of b is dead
+// once used, and its registers receive the same chunk of `next` (the row after a) if there is one: two rows of registers,
+// the loads of the next row in flight during the rest of the arithmetic, the barrier and the tile's stores.
+template <u32 TPB, u32 CPL>
+__device__ __forceinline__ void demap_symbol(const Row<TPB, CPL>& a, Row<TPB, CPL>& b, const float4* next, u32 lane_off,
+                                             u32 used, const u32* inv2, uint8_t* tile, u32 K, float gain) {
+#pragma unroll
+    for (u32 j = 0; j < CPL; j++) {
+        if (!(used >> j & 1u)) continue;
+        const u32 ent = inv2[threadIdx.x + j * TPB], n0 = ent & 0xFFFFu, n1 = ent >> 16;  // n of the two bins
+        if (n0 != UNUSED) {
+            const u32 q = soft_pair(a.v[j].x, a.v[j].y, b.v[j].x, b.v[j].y, gain);
+            tile[n0] = (uint8_t)q;
+            tile[K + n0] = (uint8_t)(q >> 8);
+        }
+        if (n1 != UNUSED) {
+            const u32 q = soft_pair(a.v[j].z, a.v[j].w, b.v[j].z, b.v[j].w, gain);
+            tile[n1] = (uint8_t)q;
+            tile[K + n1] = (uint8_t)(q >> 8);
+        }
+        if (next) b.v[j] = load_chunk<TPB>(next, j, lane_off);
+    }
+}
+
+// LDS: two tiles of tb bytes (2K rounded up to 16), then nfft u16 of the inverted table.
+template <u32 TPB, u32 CPL>
+__global__ __launch_bounds__(TPB) void vit_ofdm_demap_kernel(OfdmArgs A) {
+    extern __shared__ uint4 lds_ofdm[];  // no static LDS in this kernel: the base stays 16-byte aligned
+    const u32 K = A.K, nb = 2u * K, tb = (nb + 15u) / 16u * 16u;
+    uint8_t* tiles = reinterpret_cast<uint8_t*>(lds_ofdm);
+    uint16_t* inv = reinterpret_cast<uint16_t*>(tiles + 2u * tb);
+    const u64 t = blockIdx.x / A.runs;
+    const u32 s0 = A.lo + (u32)(blockIdx.x % A.runs) * A.run, s1 = s0 + A.run < A.hi ? s0 + A.run : A.hi;
+
+    for (u32 i = threadIdx.x; i < A.nfft / 2u; i += TPB) reinterpret_cast<u32*>(inv)[i] = UNUSED | UNUSED << 16;
+    for (u32 i = threadIdx.x; i < 2u * tb / 4u; i += TPB) reinterpret_cast<u32*>(tiles)[i] = 0x80808080u;
+    __syncthreads();
+    for (u32 n = threadIdx.x; n < K; n += TPB) {
+        const u32 b = A.bins[n];
+        if (b < A.nfft) inv[b] = (uint16_t)n;
+    }
+    __syncthreads();
+    // the lane's chunks are threadIdx.x + j*TPB; their entries (n of the two bins, low half first) stay in LDS
+    const u32* inv2 = reinterpret_cast<const u32*>(inv);
+    u32 used = 0;
+#pragma unroll
+    for (u32 j = 0; j < CPL; j++) {
+        const u32 c = threadIdx.x + j * TPB;
+        if (2u * c < A.nfft && inv2[c] != 0xFFFFFFFFu) used |= 1u << j;
+    }
+    const u32 lane_off = threadIdx.x * 16u;
+    const float4* frame = A.fft + t * A.frame_stride2;
+    Row<TPB, CPL> x, y;  // rows s and s + 1 at even s - s0, rows s + 1 and s at odd
+    load_row(frame + (u64)s0 * A.sym_stride2, lane_off, used, x);
+    load_row(frame + (u64)(s0 + 1u) * A.sym_stride2, lane_off, used, y);
+    for (u32 s = s0; s < s1; s++) {
+        uint8_t* tile = tiles + (s & 1u) * tb;
+        const float4* next = s + 1u < s1 ? frame + (u64)(s + 2u) * A.sym_stride2 : nullptr;
+        if ((s - s0) & 1u)
+            demap_symbol(x, y, next, lane_off, used, inv2, tile, K, A.gain);
+        else
+            demap_symbol(y, x, next, lane_off, used, inv2, tile, K, A.gain);
+        __syncthreads();
+        // the tile's nb bytes to their place: d_fic, or a CIF row of the ring
+        uint8_t* dst;
+        if (s < A.fic_syms) {
+            dst = A.fic + (t * A.fic_syms + s) * nb;
+        } else {
+            const u32 m = s - A.fic_syms, c = m / A.per;
+            u64 row = A.first_row + t * A.cifs + c;
+            if (row >= A.nrows) row -= A.nrows;
+            dst = A.ring + row * A.row_bytes + A.col + (u64)(m - c * A.per) * nb;
+        }
+        if (nb >= 16u) {
+            for (u32 e = threadIdx.x; e < tb / 16u; e += TPB) {
+                const u32 want = 16u * e, a = want < nb - 16u ? want : nb - 16u;  // the last chunk ends at the tile's end
+                uint4 v;
+                if (a == want) {
+                    v = *reinterpret_cast<const uint4*>(tile + a);
+                } else {
+                    u32 w[4] = {0, 0, 0, 0};
+#pragma unroll
+                    for (u32 k = 0; k < 16; k++) w[k >> 2] |= (u32)tile[a + k] << (8u * (k & 3u));
+                    v = make_uint4(w[0], w[1], w[2], w[3]);
+                }
+                __builtin_memcpy(dst + a, &v, 16);  // unaligned global_store_dwordx4
+            }
+        } else if (threadIdx.x < nb) {
+            dst[threadIdx.x] = tile[threadIdx.x];
+        }
+    }
+}
+
+template <u32 TPB, u32 CPL>
+hipError_t launch(const OfdmArgs& A, u64 grid, size_t lds, hipStream_t stream) {
+    hipLaunchKernelGGL((vit_ofdm_demap_kernel<TPB, CPL>), dim3((unsigned)grid), dim3(TPB), lds, stream, A);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+int64_t vit_freq_bins_host(uint32_t nfft, uint16_t* h_bins) {
+    if (!h_bins || (nfft != 256u && nfft != 512u && nfft != 1024u && nfft != 2048u)) return -1;
+    int64_t n = 0;
+    uint32_t p = 0;
+    for (uint32_t i = 1; i < nfft; i++) {
+        p = (13u * p + nfft / 4u - 1u) % nfft;
+        if (p >= nfft / 8u && p <= 7u * nfft / 8u && p != nfft / 2u) h_bins[n++] = (uint16_t)((p + nfft / 2u) % nfft);  // k mod nfft
+    }
+    return n;
+}
+
+hipError_t vit_launch_ofdm_demap(const float* d_fft, uint64_t sym_stride, uint64_t frame_stride, const uint16_t* d_bins,
+                                 const vit_ofdm_shape& shape, float gain, int64_t nframes, uint8_t* d_fic,
+                                 const vit_cif_ring* ring, uint64_t col, hipStream_t stream) {
+    OfdmArgs A = {};
+    A.fft = reinterpret_cast<const float4*>(d_fft);
+    A.sym_stride2 = sym_stride / 2u;
+    A.frame_stride2 = frame_stride / 2u;
+    A.bins = d_bins;
+    A.nfft = shape.nfft;
+    A.K = shape.ncarriers;
+    A.fic_syms = shape.fic_syms;
+    A.cifs = shape.cifs;
+    A.per = (shape.nsyms - 1u - shape.fic_syms) / shape.cifs;
+    A.lo = d_fic ? 0u : shape.fic_syms;
+    A.hi = ring ? shape.nsyms - 1u : shape.fic_syms;
+    A.gain = gain;
+    A.fic = d_fic;
+    if (ring) {
+        A.ring = const_cast<uint8_t*>(ring->d_base);  // this call is the ring's writer
+        A.row_bytes = ring->row_bytes;
+        A.nrows = ring->nrows;
+        A.first_row = ring->first_row;
+        A.col = col;
+    }
+    if (nframes <= 0 || A.hi <= A.lo) return hipSuccess;
+    // Runs: about 8 workgroups per CU over the whole grid (all the CU can hold: 4 waves each), RUN_MAX symbols at most.
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    const u64 target = 8ull * (u64)vit_device_cus(dev);
+    const u32 nsym = A.hi - A.lo;
+    u64 rpf = (target + (u64)nframes - 1) / (u64)nframes;
+    if (rpf > nsym) rpf = nsym;
+    u32 run = (u32)((nsym + rpf - 1) / rpf);
+    if (run > RUN_MAX) run = RUN_MAX;
+    A.run = run;
+    A.runs = (nsym + run - 1) / run;
+    const u64 grid = (u64)nframes * A.runs;
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const size_t lds = 2u * (size_t)((2u * A.K + 15u) / 16u * 16u) + 2u * (size_t)A.nfft;
+    const u32 chunks = A.nfft / 2u;
+    if (chunks <= 256u) return launch<256, 1>(A, grid, lds, stream);
+    if (chunks <= 512u) return launch<256, 2>(A, grid, lds, stream);
+    if (chunks <= 1024u) return launch<256, 4>(A, grid, lds, stream);
+    if (chunks <= 2048u) return launch<1024, 2>(A, grid, lds, stream);
+    return launch<1024, 4>(A, grid, lds, stream);
+}
