@@ -36,6 +36,7 @@ def lib():
         L.vo_deconvolve_opt.argtypes = [C.c_uint, vp, vp, C.c_int]
         L.vo_deconvolve_u8.argtypes = [C.c_uint, vp, vp]
         L.vo_trace_state0_u8.argtypes = [C.c_uint, vp, C.c_int, vp]
+        L.vo_decisions_u8.argtypes = [C.c_uint, vp, C.c_int, vp]
         L.vo_decode_batch_u8.argtypes = [C.c_uint, vp, vp, C.c_long, C.c_int]
         L.vo_decode_batch_u8_opt.argtypes = [C.c_uint, vp, vp, C.c_long, C.c_int, C.c_int]
         L.vo_deconvolve_avx2_u8.argtypes = [C.c_uint, vp, vp]
@@ -128,6 +129,15 @@ def trace_state0(framebits, sym_u8, ge=False):
     tr = np.zeros(framebits + 6, np.uint8)
     assert lib().vo_trace_state0_u8(framebits, _p(sym_u8), 1 if ge else 0, _p(tr)) == 0
     return tr
+
+
+def decisions(framebits, sym_u8, ge=False):
+    """the decision words ChainBack consumes: framebits+6 uint64, bit s of word t = decision of state s at trellis step t"""
+    sym_u8 = np.ascontiguousarray(sym_u8, np.uint8)
+    assert sym_u8.size == sym_len(framebits)
+    dec = np.zeros(framebits + 6, np.uint64)
+    assert lib().vo_decisions_u8(framebits, _p(sym_u8), 1 if ge else 0, _p(dec)) == 0
+    return dec
 
 
 def decode_batch(framebits, sym_u8, nthreads=1, avx2=False, ge=False):

@@ -82,16 +82,21 @@ static void vo_chainback(unsigned framebits, const uint64_t *dec,
     }
 }
 
+static int vo_decode_core_d(unsigned framebits, const uint32_t *s32,
+                            const uint8_t *s8, unsigned char *out, int ge, uint8_t *trace0, uint64_t *dec_out);
 static int vo_decode_core_t(unsigned framebits, const uint32_t *s32,
-                            const uint8_t *s8, unsigned char *out, int ge, uint8_t *trace0);
+                            const uint8_t *s8, unsigned char *out, int ge, uint8_t *trace0) {
+    return vo_decode_core_d(framebits, s32, s8, out, ge, trace0, NULL);
+}
 static int vo_decode_core(unsigned framebits, const uint32_t *s32,
                           const uint8_t *s8, unsigned char *out, int ge) {
     return vo_decode_core_t(framebits, s32, s8, out, ge, NULL);
 }
 /* trace0 (optional, framebits+6 entries): the metric of state 0 after every trellis step, after the renormalisation
  * where there is one - what tests/test_oracle_kat.py checks against a hand-derived trajectory */
-static int vo_decode_core_t(unsigned framebits, const uint32_t *s32,
-                            const uint8_t *s8, unsigned char *out, int ge, uint8_t *trace0) {
+/* dec_out (optional, framebits+6 entries): the decision words, copied from the very array vo_chainback has just consumed */
+static int vo_decode_core_d(unsigned framebits, const uint32_t *s32,
+                            const uint8_t *s8, unsigned char *out, int ge, uint8_t *trace0, uint64_t *dec_out) {
     if (framebits > VO_MAXBITS) return 1;
     vo_init_masks();
     uint64_t dec[VO_MAXBITS + 6]; /* deconvolve.cpp:93,127: on the stack */
@@ -117,6 +122,7 @@ static int vo_decode_core_t(unsigned framebits, const uint32_t *s32,
         if (trace0) trace0[t - 1] = a[0];
     }
     vo_chainback(framebits, dec, out);
+    if (dec_out) memcpy(dec_out, dec, sizeof(uint64_t) * (framebits + 6));
     return 0;
 }
 
@@ -142,6 +148,13 @@ int vo_deconvolve_u8_ge(unsigned framebits, const uint8_t *symbols,
 int vo_trace_state0_u8(unsigned framebits, const uint8_t *symbols, int ge, uint8_t *trace0) {
     unsigned char out[(VO_MAXBITS + 7) / 8];
     return vo_decode_core_t(framebits, NULL, symbols, out, ge, trace0);
+}
+
+/* the decision history of one frame: bit s of dec[t] = decision of state s at trellis step t (what ChainBack reads;
+ * tests/tbdirect.py models the kernels' block-parallel tracebacks on it) */
+int vo_decisions_u8(unsigned framebits, const uint8_t *symbols, int ge, uint64_t *dec) {
+    unsigned char out[(VO_MAXBITS + 7) / 8];
+    return vo_decode_core_d(framebits, NULL, symbols, out, ge, NULL, dec);
 }
 
 /* ---- batch drivers --------------------------------------------------------- */

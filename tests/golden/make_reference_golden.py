@@ -8,8 +8,10 @@ the digests of the inputs.  Every C variant this CPU runs (at 9216 bits: the 256
 RS: per seeded superframe the return value, the digest of the sentinel-initialised output, the digest of the input.
 RS paths (reference_rs_paths.npy): the same four values for the syndrome-directed tables of tests/rsdirect.py
 (pinned_tables(): 64 columns of every class on their own, the first-failure, wide and export tables).
+Traceback paths (reference_tb_paths.npy): per merge-directed frame of tests/tbdirect.py (tests/golden/tb_directed.json) its
+length, the digest of its symbols and the digests of the reference's output under both thresholds.
 
-Arguments select the parts to (re)write - decoder, rs, rs_paths - default all; reference_provenance.json is updated
+Arguments select the parts to (re)write - decoder, rs, rs_paths, tb_paths - default all; reference_provenance.json is updated
 for the parts written.
 """
 import datetime
@@ -26,9 +28,11 @@ sys.path.insert(0, os.path.dirname(HERE))
 import _vitpkg  # noqa: E402
 import reffix  # noqa: E402
 import rsdirect  # noqa: E402
+import tbdirect  # noqa: E402
 
-PARTS = set(sys.argv[1:]) or {"decoder", "rs", "rs_paths"}
-assert PARTS <= {"decoder", "rs", "rs_paths"}, PARTS
+ALL_PARTS = {"decoder", "rs", "rs_paths", "tb_paths"}
+PARTS = set(sys.argv[1:]) or ALL_PARTS
+assert PARTS <= ALL_PARTS, PARTS
 
 R = _vitpkg.load_ref()
 assert R.build(), "oracle/_ref is missing and there is no reference checkout to build it from"
@@ -66,9 +70,17 @@ if "rs_paths" in PARTS:
     np.save(rsdirect.RS_PATHS_NPY, paths)
     assert os.path.getsize(rsdirect.RS_PATHS_NPY) < os.path.getsize(os.path.join(HERE, "golden.json"))
 
+if "tb_paths" in PARTS:
+    def _ref_decode(fb, sym, ge):
+        got = [R.decode_batch(fb, sym, variant=v, ge=ge, nthreads=1)[0] for v in R.variants(fb)]
+        assert got and all(np.array_equal(got[0], g) for g in got[1:]), ("the reference's variants disagree", fb, ge)
+        return got[0]
+    tb = tbdirect.pinned_rows(_ref_decode, reffix.fnv1a64_rows)
+    np.save(tbdirect.TB_PATHS_NPY, tb)
+
 info = R.build_info()
 prov = {}
-if PARTS != {"decoder", "rs", "rs_paths"}:
+if PARTS != ALL_PARTS:
     with open(reffix.PROVENANCE_JSON) as f:
         prov = json.load(f)
 if PARTS & {"decoder", "rs"}:
@@ -83,6 +95,12 @@ if "rs_paths" in PARTS:
                         "reference_tag": R.REFERENCE_TAG, "compiler": info.get("compiler"), "date": datetime.date.today().isoformat(),
                         "superframes": int(paths.shape[0]), "reference_counts": paths_counts,
                         "class_digests": rsdirect.class_digests()}
+if "tb_paths" in PARTS:
+    prov["tb_paths"] = {"what": "reference_tb_paths.npy: deconvolve.cpp (thresholds 150 and 149) on the merge-directed frames of "
+                                "tests/tbdirect.py (tests/golden/tb_directed.json)",
+                        "reference_tag": R.REFERENCE_TAG, "compiler": info.get("compiler"), "date": datetime.date.today().isoformat(),
+                        "frames": int(tb.shape[0]), "variants_agreeing": variants,
+                        "frames_on_which_the_thresholds_differ": int((tb[:, 2] != tb[:, 3]).sum())}
 with open(reffix.PROVENANCE_JSON, "w") as f:
     json.dump(prov, f, indent=1)
 print("wrote", sorted(PARTS), "variants", variants)

@@ -16,6 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 if HERE not in sys.path:
     sys.path.insert(0, HERE)
 import reffix  # noqa: E402
+import tbdirect  # noqa: E402
 
 GE_COL = {0: (2, 4), 1: (3, 5)}  # renorm_ge -> (column of the soft family, column of the hard family)
 
@@ -92,6 +93,38 @@ def test_uniform_length_entry(V, torch_cuda, fix, kernel, ge):
             if kernel == 0:  # the drop-in export, reference ABI (u32 symbols)
                 rc, one = V.deconvolve(fb, hard[i].astype(np.uint32))
                 assert rc == 0 and reffix.fnv1a64(one) == int(tab[i, GE_COL[ge][1]]), (fb, ge)
+    finally:
+        V.set_renorm_ge(old_ge)
+        V.set_kernel(old)
+
+
+@pytest.mark.parametrize("ge", [0, 1], ids=["gt150", "ge150"])
+@pytest.mark.parametrize("kernel", [0, 1, 2, 3])
+def test_merge_directed_frames(V, torch_cuda, kernel, ge):
+    """the traceback-directed set of tests/tbdirect.py (every path of the block-parallel tracebacks: tests/test_tb_paths_host.py)
+    against the recorded outputs of the reference's decoders, no oracle: one descriptor table of all frames, and the
+    uniform-length entry per length in whole waves"""
+    torch = torch_cuda
+    rows = np.load(tbdirect.TB_PATHS_NPY)
+    specs = tbdirect.pinned_specs()
+    syms = [s.symbols() for s in specs]
+    assert rows.shape == (len(specs), len(tbdirect.PIN_COLS))
+    assert np.array_equal(reffix.fnv1a64_rows(syms), rows[:, 1]), "traceback path generator drifted"
+    want = rows[:, 3 if ge else 2]
+    fbs = [s.fb for s in specs]
+    dig = _table_digests(V, torch, syms, fbs, kernel, ge)
+    bad = np.flatnonzero(dig != want)
+    assert bad.size == 0, "kernel %d ge %d: %d frames differ from the reference, first recipes: %s" % (
+        kernel, ge, bad.size, [specs[b].key() for b in bad[:4]])
+    old, old_ge = V.set_kernel(kernel), V.set_renorm_ge(ge)
+    try:
+        for fb in sorted(set(fbs)):
+            idx = [i for i, f in enumerate(fbs) if f == fb]
+            idx = (idx * 4)[:max(4, len(idx) // 4 * 4)]  # whole groups of four equally long frames
+            d_out = torch.full((len(idx), (fb + 7) // 8), 0xEE, dtype=torch.uint8, device="cuda")
+            V.decode_batch_dev(torch.from_numpy(np.stack([syms[i] for i in idx])).cuda(), d_out, fb, len(idx))
+            torch.cuda.synchronize()
+            assert np.array_equal(reffix.fnv1a64_rows(list(d_out.cpu().numpy())), want[idx]), (fb, kernel, ge)
     finally:
         V.set_renorm_ge(old_ge)
         V.set_kernel(old)

@@ -19,6 +19,7 @@ if HERE not in sys.path:
 import _vitpkg  # noqa: E402
 import reffix  # noqa: E402
 import rsdirect  # noqa: E402
+import tbdirect  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -100,6 +101,18 @@ def test_large_batch_and_comparator_non_vacuity(R, O):
             _all_agree(R, O, fb, hard, True)
             differ = (R.decode_batch(fb, hard) != R.decode_batch(fb, hard, ge=True)).any(axis=1)
             assert differ.sum() >= 1, (fb, name)
+
+
+@pytest.mark.parametrize("ge", [False, True], ids=["gt150", "ge150"])
+def test_merge_directed_frames(R, O, ge):
+    """every frame of the traceback-directed set (tests/tbdirect.py: erasure, near-erasure, uniform and hard bursts on
+    noise-free, noisy and hard-decision bases): all variants == the oracle"""
+    by_fb = {}
+    for sp in tbdirect.pinned_specs():
+        by_fb.setdefault(sp.fb, []).append(sp.symbols())
+    assert len(by_fb) >= 20 and sum(len(v) for v in by_fb.values()) >= 200
+    for fb, syms in by_fb.items():
+        _all_agree(R, O, fb, np.stack(syms), ge)
 
 
 @pytest.mark.parametrize("ge", [False, True], ids=["gt150", "ge150"])
@@ -229,11 +242,14 @@ def test_reference_build_reproduces_its_committed_fixtures(R):
             for p, r, o in zip(P, *R.rs_check_batch(P, rsdims, np.full((P.shape[0], 110 * rsdims), reffix.RS_SENTINEL, np.uint8)))]
     assert np.array_equal(np.array(rows, np.uint64), rs)
     assert np.array_equal(rsdirect.pinned_rows(R.rs_check_batch), np.load(rsdirect.RS_PATHS_NPY))  # the syndrome-directed tables
+    tb = tbdirect.pinned_rows(lambda fb, sym, ge: R.decode_batch(fb, sym, ge=ge)[0], reffix.fnv1a64_rows)  # the merge-directed frames
+    assert np.array_equal(tb, np.load(tbdirect.TB_PATHS_NPY))
 
 
 def test_oracle_reproduces_the_reference_fixtures(O):
     """NEVER SKIPS: needs neither oracle/_ref nor a reference checkout.  The oracle reproduces every committed digest of the
-    reference's outputs - 4608 lengths x {soft, hard} x {> 150, >= 150} - and every RS return value and output digest.
+    reference's outputs - 4608 lengths x {soft, hard} x {> 150, >= 150}, the merge-directed frames of tests/tbdirect.py -
+    and every RS return value and output digest.
     The inputs are rebuilt from their seeds and checked against their own digests first."""
     tab = np.load(reffix.DECODER_NPY)
     assert tab.shape == (len(reffix.LENGTHS), len(reffix.COLS)) and tab.dtype == np.uint64
@@ -269,5 +285,13 @@ def test_oracle_reproduces_the_reference_fixtures(O):
     assert np.array_equal(got, paths), np.flatnonzero((got != paths).any(axis=1))[:8]
     prets = np.ascontiguousarray(paths[:, 1]).view(np.int64)
     assert (paths[:, 0] == 1).sum() >= 64 * 48 and (prets[paths[:, 0] == 1] == 6).sum() >= 64  # degree-6 locators, accepted
+    # the merge-directed frames (tests/tbdirect.py): input digests, then the output digests under both comparators
+    tb = np.load(tbdirect.TB_PATHS_NPY)
+    got = tbdirect.pinned_rows(lambda fb, sym, ge: O.decode_batch(fb, sym, ge=ge)[0], reffix.fnv1a64_rows)
+    assert got.shape == tb.shape and np.array_equal(got[:, :2], tb[:, :2]), "traceback path generator drifted"
+    assert np.array_equal(got, tb), np.flatnonzero((got != tb).any(axis=1))[:8]
+    assert (tb[:, 2] != tb[:, 3]).sum() >= 9  # the hard-decision bases: the comparators decode them differently
     with open(reffix.PROVENANCE_JSON) as f:
-        assert json.load(f)["reference_tag"] == "2024_10_08"
+        prov = json.load(f)
+    assert prov["reference_tag"] == "2024_10_08"
+    assert prov["tb_paths"]["frames"] == tb.shape[0]

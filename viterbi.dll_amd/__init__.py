@@ -14,7 +14,8 @@ import os
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("VITERBI_AMD_LIB") or os.path.join(_HERE, "libviterbi.so")  # env: kernel experiments
+LIB_PATH_DEFAULT = os.path.join(_HERE, "libviterbi.so")
+LIB_PATH = os.environ.get("VITERBI_AMD_LIB") or LIB_PATH_DEFAULT  # env: kernel experiments, the tests' -DVIT_DIAG_SPEC build
 MAX_FRAMEBITS = 9216
 TAIL = 6
 

@@ -379,6 +379,19 @@ constexpr u32 TB_WARM = VIT_TB_WARM;  // warm-up steps (multiple of 5) a specula
 #endif
 constexpr u32 TB_WARM_HARD = VIT_TB_WARM_HARD, TB_HARD_MISSES = VIT_TB_HARD_MISSES;
 
+#ifdef VIT_DIAG_SPEC  /* test build: what the traceback did.  The long-frame kernel's fast groups - [0] groups, [1] parts traced in flight,
+                        [2] groups that gave up tracing in flight (input without signal), [3] parts traced after the forward pass beyond
+                        part 0, [4] of those: parts that had been traced in flight and failed their check.  Every packed kernel - [5] blocks
+                        of the fast form (parts traced from a known top) that missed in the first pass, [6] re-trace passes the fast form
+                        ran, [7] general-form parts whose first pass switched the wave to the long warm-up.
+                        tests/test_gpu_tb_paths.py compares all eight with tests/tbdirect.py's models. */
+__device__ unsigned long long g_diag_spec[8];
+#define SPEC_COUNT(i) do { if (lane == 0) atomicAdd(&g_diag_spec[i], 1ull); } while (0)
+#define SPEC_COUNT_N(i, n) do { if (lane == 0) atomicAdd(&g_diag_spec[i], (unsigned long long)(n)); } while (0)
+#else
+#define SPEC_COUNT(i) do { } while (0)
+#endif
+
 // LDS byte offset, inside a 512-byte decision block, of the (acc1, acc0) pair of ACS lane `lane`:
 // [pair][31 - l][1 - n] - the register with n = 1 first.  Every store of a block uses it.
 DEV u32 dec_slot(u32 lane) { return acs_pair(lane) * 256u + (31u - acs_l5(lane)) * 8u; }
@@ -487,6 +500,9 @@ u32 traceback_part(const char* dec, u32* scratch, u32* img, u32 fstride, u32 lan
         const bool changed = has_work && !fixed && new_in != P_in;
         const unsigned long long miss = __ballot(changed);
         if (miss == 0) break;
+#ifdef VIT_DIAG_SPEC
+        if (pass == 0 && warm == TB_WARM && (u32)__popcll(miss) >= TB_HARD_MISSES) SPEC_COUNT(7);
+#endif
         if (pass == 0 && warm == TB_WARM && (u32)__popcll(miss) >= TB_HARD_MISSES) warm = TB_WARM_HARD;  // for the parts that follow
         if (changed) P_in = new_in;
         P = new_in;
@@ -609,6 +625,13 @@ DEV u32 traceback_part16(const char* dec, u32* img, u32 fstride, u32 lane, u32 l
             if (pass == 0) *misses = (u32)__popcll(miss);
             if (miss == 0) break;
         } else {
+#ifdef VIT_DIAG_SPEC
+            {
+                const unsigned long long miss = __ballot(changed);
+                if (pass == 0) SPEC_COUNT_N(5, __popcll(miss));
+                if (miss) SPEC_COUNT(6);
+            }
+#endif
             if (!__any(changed)) break;
         }
         if (changed) {
@@ -1014,14 +1037,6 @@ DEV u32 pack_rows(u32 P) {
            ((u32)__builtin_amdgcn_readlane((int)P, 32) << 16) | ((u32)__builtin_amdgcn_readlane((int)P, 48) << 24);
 }
 
-#ifdef VIT_DIAG_SPEC  /* test build: what the fast groups did - [0] groups, [1] parts traced in flight, [2] groups that gave up tracing in
-                        flight (input without signal), [3] parts traced after the forward pass beyond part 0, [4] of those: parts that had
-                        been traced in flight and failed their check */
-__device__ unsigned long long g_diag_spec[8];
-#define SPEC_COUNT(i) do { if (lane == 0) atomicAdd(&g_diag_spec[i], 1ull); } while (0)
-#else
-#define SPEC_COUNT(i) do { } while (0)
-#endif
 #ifndef VIT_LONG_BASE_PRIO
 #define VIT_LONG_BASE_PRIO 1
 #endif
