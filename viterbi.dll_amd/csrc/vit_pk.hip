@@ -312,13 +312,13 @@ constexpr u32 SEG_BLOCKS = VREG_BLOCKS + DUMP_GROUP + 1u;  // 49 blocks = 784 st
 //   nb <= 17 : R = 0,                Ld = nb - 1
 //   else     : R = min(32, nb - 17), Ld = nb - R - 1  (>= 16 = one dump group)
 // Frames longer than a segment take vit_pk_long_kernel below (blocks beyond the last 17 go through HBM).
-__host__ __device__ inline u32 pk_reg_blocks(u32 nb) {
+__host__ __device__ constexpr inline u32 pk_reg_blocks(u32 nb) {
     if (nb <= DUMP_GROUP + 1u) return 0;
     const u32 r = nb - (DUMP_GROUP + 1u);
     return r < VREG_BLOCKS ? r : VREG_BLOCKS;
 }
-__host__ __device__ inline u32 pk_img_stride(u32 maxfb) { return ((maxfb + 31u) >> 5) + 2u; }  // dwords per frame
-__host__ __device__ inline u32 pk_scratch_words(u32 maxfb) {
+__host__ __device__ constexpr inline u32 pk_img_stride(u32 maxfb) { return ((maxfb + 31u) >> 5) + 2u; }  // dwords per frame
+__host__ __device__ constexpr inline u32 pk_scratch_words(u32 maxfb) {
     // words per lane of traceback bit scratch: the longest part is a segment's LDS tail (<= 17 blocks)
     // or a 256-step register group -> BL <= 20 for full segments; short frames are all "tail"
     u32 nblk = (maxfb + VIT_TAIL + 15u) >> 4;
@@ -334,9 +334,9 @@ struct PkLayout {
     u32 total;
     u32 maxfb;      // the framebits this layout was sized for
 };
-__host__ __device__ inline PkLayout pk_layout(u32 maxfb) {  // single-segment kernel (nblk <= 49)
+__host__ __device__ constexpr inline PkLayout pk_layout(u32 maxfb) {  // single-segment kernel (nblk <= 49)
     const u32 nb = (maxfb + VIT_TAIL + 15u) >> 4;
-    PkLayout l;
+    PkLayout l{};
     l.maxfb = maxfb;
     l.dec_bytes = (nb - pk_reg_blocks(nb) - 1u) * DEC_BLOCK;
     const u32 scratch = 64u * 4u * pk_scratch_words(maxfb), img = 16u * pk_img_stride(maxfb);
@@ -546,6 +546,31 @@ u32 traceback_part(const char* dec, u32* scratch, u32* img, u32 fstride, u32 lan
 struct Tb16 {
     u32 sh[5], jj[5], mk[5];  // by ii mod 5: JJ - 2, JJ, (1 << JJ) | 4 with JJ = 7 - ((t - 1) mod 5), t = tbase + ii
 };
+DEV Tb16 tb16_lane(u32 tbase) {  // tbase = the first step of the lane's block
+    Tb16 L;
+    const u32 c = (tbase + 4u) % 5u;  // (tbase - 1) mod 5
+#pragma unroll
+    for (int r = 0; r < 5; r++) {
+        const u32 e = (c + r) % 5u, JJ = 7u - e;
+        L.sh[r] = JJ - 2u;
+        L.jj[r] = JJ;
+        L.mk[r] = (1u << JJ) | 4u;
+    }
+    return L;
+}
+// the triples of a block that starts s steps (mod 5) lower: (tbase - s - 1 + r) mod 5 = (tbase - 1 + (r - s)) mod 5
+template <u32 S>
+DEV Tb16 tb16_rotate(const Tb16& a) {
+    Tb16 L;
+#pragma unroll
+    for (int r = 0; r < 5; r++) {
+        const int k = (r + 5 - (int)(S % 5u)) % 5;
+        L.sh[r] = a.sh[k];
+        L.jj[r] = a.jj[k];
+        L.mk[r] = a.mk[k];
+    }
+    return L;
+}
 DEV u32 bfi_v(u32 mask, u32 a, u32 b) {
     u32 d;
     asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(d) : "v"(mask), "v"(a), "v"(b));
@@ -578,9 +603,11 @@ struct Tb16Run {
 // that equals what the part above ends in, which the caller checks once the frame's last part has been traced from the true end
 // state.  *misses = speculative blocks of the wave that missed in the first pass.  TOMEM (gout = per lane: its frame's output):
 // the lane's 16 decoded bits go straight to memory as two MSB-first bytes (deconvolve.cpp:432-433) instead of into the LDS image.
-template <bool SPEC = false, bool TOMEM = false>
+// GEO (the fixed-geometry kernel, vit_pk_fixed_kernel): lo, nl and slot0 are compile-time constants of the caller, which also
+// hands in the five per-lane triples (*geo: they only rotate from part to part) and has checked the LDS layout statically.
+template <bool SPEC = false, bool TOMEM = false, bool GEO = false>
 DEV u32 traceback_part16(const char* dec, u32* img, u32 fstride, u32 lane, u32 lo, u32 nl, u32 slot0, u32 P_top, u32 dmask,
-                         uint8_t* gout = nullptr, u32* p_spec = nullptr, u32* misses = nullptr) {
+                         uint8_t* gout = nullptr, u32* p_spec = nullptr, u32* misses = nullptr, const Tb16* geo = nullptr) {
 #ifdef VIT_DIAG_NO_TB
     return P_top;
 #endif
@@ -592,10 +619,14 @@ DEV u32 traceback_part16(const char* dec, u32* img, u32 fstride, u32 lane, u32 l
     const bool fixed = has_work && above <= 2u;  // its warm-up would cross the part's top: it starts there, from the true position
     const u32 C = (fi >> 1) * 256u + (fi & 1u) * 2u;
     const u32 dbase = (u32)(uintptr_t)(const __attribute__((address_space(3))) char*)dec;
-    if (dbase & 511u) __builtin_trap();
+    if constexpr (!GEO) {
+        if (dbase & 511u) __builtin_trap();
+    }
     const u32 bbq = dbase + ((lo >> 4) - slot0 + q) * DEC_BLOCK;
     Tb16 L;
-    {
+    if constexpr (GEO) {
+        L = *geo;
+    } else {  // (= tb16_lane(tbase), written out: through the helper the general kernels' set-up code comes out in another order)
         const u32 c = (tbase + 4u) % 5u;  // (tbase - 1) mod 5
 #pragma unroll
         for (int r = 0; r < 5; r++) {
@@ -935,6 +966,265 @@ __global__ __launch_bounds__(64, 4) void vit_pk_kernel(const uint8_t* __restrict
                 const u32 byte = (im[b >> 2] >> (8u * (b & 3u))) & 0xFFu;
                 o[b] = (uint8_t)(__builtin_bitreverse32(byte) >> 24);
             }
+        }
+    }
+}
+
+// ---- fixed geometry: a uniform batch of frames of ONE length known at compile time (the FIC's 768 bits) ------------------------
+// vit_pk_kernel pays for what such a launch never uses: four possibly different frames per wave (descriptor or uniform branch,
+// 64-bit offsets, validity checks, per-lane selects), run-time block geometry (register or LDS history per block, a predicate
+// on every symbol prefetch), the set-up of every traceback part (tbase mod 5, fifteen per-lane values, three times), a window
+// move with run-time bounds, and the general traceback form, whose 25 spilled VGPRs make every wave a scratch-using wave.  Here
+// the frame length FB is a template parameter: frame addresses are scalar arithmetic on blockIdx.x, the block loop is cut where
+// the history moves from registers to LDS, the traceback parts and the window moves have constant bounds, and only the fast
+// traceback form is compiled in (no private segment).  Same arithmetic, same traceback fixed point: the same bytes.
+// Another uniform length (FB = 32*m <= 768) is one more instantiation plus its line in vit_launch_pk.
+#ifndef VIT_FIC_FIXED
+#define VIT_FIC_FIXED 1  /* 0: the library without the fixed-geometry instantiation (A/B runs; the general path at 768 bits) */
+#endif
+#ifndef VIT_FIC_FIXED_SPLIT
+#define VIT_FIC_FIXED_SPLIT 1  /* 1: one loop over the register-history pairs and one over the LDS pairs (twenty block bodies, 67 KB of
+                                  code); 0: one loop, the choice per block by a scalar test (ten bodies, 41 KB).  The smaller code is
+                                  the SLOWER one: 0.4330-0.4343 ms against 0.4122-0.4141 on the benchmark batch, the general
+                                  kernel 0.4186-0.4205.  On input without signal it is the other way round, and the general
+                                  kernel beats both: DESIGN.md (d), profiles/r09_fic_fixed_ab.txt section 3 */
+#endif
+template <u32 FB>
+struct PkFixed {
+    static constexpr u32 T = FB + VIT_TAIL;            // trellis steps
+    static constexpr u32 NB = (T + 15u) >> 4;          // blocks; the last one has six steps
+    static constexpr u32 R = pk_reg_blocks(NB);        // blocks [0,R) keep their history in VGPRs
+    static constexpr u32 LD = NB - R - 1u;             // blocks [R, NB-1) go to dec, the last one onto the dead table
+    static constexpr u32 TAB_OFF = LD * DEC_BLOCK;
+    static constexpr u32 IMG_OFF = TAB_OFF + DEC_BLOCK;  // the image follows the last block (no traceback scratch words here)
+    static constexpr u32 FSTRIDE = FB / 32u;           // image dwords per frame: every halfword is written by exactly one lane
+    static constexpr u32 LDS_BYTES = TAB_OFF + (u32)TAB_BYTES;
+    static constexpr u32 SYM_STEPS = T;                // symbols per frame in memory: 4 per step
+    static constexpr u32 OUT_BYTES = FB / 8u;
+    static_assert(FB % 32u == 0 && FB >= 32u, "whole image dwords, an even number of 16-step blocks below the last one");
+    static_assert(VIT_STEPS6 && (T & 15u) == 6u, "the last block has six steps");
+    static_assert(NB <= SEG_BLOCKS && (R & 1u) == 0 && (LD & 1u) == 0 && R + 3u <= NB, "one segment, cut into pairs of blocks");
+    static_assert(LD <= DUMP_GROUP, "the traceback window is dec + one block");
+    static_assert(IMG_OFF + 16u * FSTRIDE <= LDS_BYTES, "the image fits the dead table region");
+    static_assert(TAB_OFF % 512u == 0, "tb16_step selects the block with the address bits above 511");
+    static_assert(LDS_BYTES == pk_layout(FB).total, "as many waves per CU as the general kernel");
+};
+
+// the parts of the fast traceback, top down: [LO, HI) with the window's slot 0 = block SLOT0; then the window moves down
+template <class G, u32 HI, u32 SLOT0>
+DEV void fixed_traceback(char* dec, u32* img, u32 lane, u32 dslot, const v32u r0, const v32u r1, u32 P, const Tb16 L) {
+    constexpr u32 LO = HI > 256u + VIT_TAIL ? HI - 256u : VIT_TAIL;
+    static_assert(LO % 16u == VIT_TAIL && (LO >> 4) >= SLOT0 && (HI >> 4) - SLOT0 <= DUMP_GROUP, "the part lies in the window");
+    P = traceback_part16<false, false, true>(dec, img, G::FSTRIDE, lane, LO, (HI - LO) >> 4, SLOT0, P, 0xFFFFFFFFu, nullptr,
+                                             nullptr, nullptr, &L);
+    if constexpr (LO != VIT_TAIL) {
+        // what stays goes D slots up (every lane moves its own 8 bytes of a block), the D register blocks below come in
+        constexpr u32 D = SLOT0 < DUMP_GROUP ? SLOT0 : DUMP_GROUP, G0 = SLOT0 - D;
+        static_assert(D >= 1u, "there are blocks below this part");
+        constexpr u32 LO2 = LO > 256u + VIT_TAIL ? LO - 256u : VIT_TAIL;
+        __syncthreads();
+#pragma unroll
+        for (u32 sl = DUMP_GROUP; sl >= D; sl--)
+            *reinterpret_cast<uint2*>(dec + sl * DEC_BLOCK + dslot) = *reinterpret_cast<const uint2*>(dec + (sl - D) * DEC_BLOCK + dslot);
+#pragma unroll
+        for (u32 b = G0; b < SLOT0; b++)
+            *reinterpret_cast<uint2*>(dec + (b - G0) * DEC_BLOCK + dslot) = make_uint2(r1[b], r0[b]);
+        __syncthreads();
+        fixed_traceback<G, LO, G0>(dec, img, lane, dslot, r0, r1, P, tb16_rotate<LO - LO2>(L));
+    }
+}
+
+template <u32 FB, bool SYM32, bool ROT>
+__global__ __launch_bounds__(64, 4) void vit_pk_fixed_kernel(const uint8_t* __restrict__ sym, uint8_t* __restrict__ out,
+                                                              long long nframes, u32 renorm_c) {
+    typedef PkFixed<FB> G;
+#ifdef VIT_DIAG_TIMES
+    const unsigned long long diag_t0 = __builtin_amdgcn_s_memrealtime();
+#endif
+    __shared__ __attribute__((aligned(512))) char lds[G::LDS_BYTES];
+    char* dec = lds;               // [block - R][lane] -> (acc1, acc0); the last block spills into tab
+    char* tab = lds + G::TAB_OFF;  // [tau][pair][c] -> M; after the ACS: last block, image
+    u32* img = reinterpret_cast<u32*>(lds + G::IMG_OFF);
+    const u32 lane = threadIdx.x;
+    u32 prio_slot = 0;
+#if VIT_PRIO
+    {  // one wave of the four of a SIMD at low priority (see vit_pk_kernel)
+        u32 hwid;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+        prio_slot = hwid & 3u;
+        switch (VIT_PRIO_MAP(hwid & 3u)) {
+            case 0: __builtin_amdgcn_s_setprio(0); break;
+            case 1: __builtin_amdgcn_s_setprio(1); break;
+            case 2: __builtin_amdgcn_s_setprio(2); break;
+            default: __builtin_amdgcn_s_setprio(3); break;
+        }
+    }
+#endif
+    // ---- frames: group g = frames 4g .. 4g + 3, each SYM_STEPS x 4 symbols in and OUT_BYTES out.  The launch's last group may
+    // have fewer: its missing frames alias the group's first frame (no symbol byte read that belongs to no frame) and their
+    // output stores are predicated off (nvalid, wave-uniform)
+    constexpr u32 SB = SYM32 ? 4u : 1u, STEP_BYTES = 4u * SB, FRAME_BYTES = G::SYM_STEPS * STEP_BYTES;
+    const long long f0 = (long long)blockIdx.x * 4;
+    const long long left = nframes - f0;
+    const u32 nvalid = left >= 4 ? 4u : (u32)left;
+    const uint8_t* gsym = sym + (size_t)f0 * FRAME_BYTES;
+    uint8_t* gout = out + (size_t)f0 * G::OUT_BYTES;
+
+    // ---- ACS lane constants ----
+    const u32 l5 = acs_l5(lane);
+    const u32 dslot = dec_slot(lane);
+    Lanes L;
+    load_toff(L, lane);
+#if VIT_TAB_STATIC
+    Lanes L1;
+    {
+        const u32 tb = (u32)(uintptr_t)(const __attribute__((address_space(3))) char*)tab;
+#pragma unroll
+        for (int rho = 0; rho < 5; rho++) {
+            L.toff[rho] += tb;
+            L1.toff[rho] = L.toff[rho] + 1024u;
+            asm volatile("" : "+v"(L1.toff[rho]));
+        }
+    }
+#endif
+    Consts C;
+    C.hi = HI;
+    C.rc = renorm_c;
+    asm volatile("" : "+v"(C.hi));
+    // ---- pre-pass lane constants: lane = (tau = lane>>1, pair pp = lane&1); frames 2pp (half 0) and 2pp + 1 (half 1) ----
+    const u32 tau = lane >> 1, pp = lane & 1u;
+    u32 ka = 2u * pp, kb = 2u * pp + 1u;
+    if (nvalid < 4u) {
+        ka = ka < nvalid ? ka : 0u;
+        kb = kb < nvalid ? kb : 0u;
+    }
+    const u32 a_off = ka * FRAME_BYTES + tau * STEP_BYTES, b_off = kb * FRAME_BYTES + tau * STEP_BYTES;  // from gsym
+    typedef typename RawStep<SYM32>::type Raw;
+    auto load32 = [&](u32 off, u32 rb) {  // the lane's step of the 32 that start at block rb (rb wave-uniform)
+        return *reinterpret_cast<const Raw*>(gsym + (size_t)rb * (16u * STEP_BYTES) + off);
+    };
+    u32 sel[4];
+    {
+        const u32 hb = (tau & 1u) ? 0x0C000C00u : 0x0D000D00u;
+#pragma unroll
+        for (int k = 0; k < 4; k++) sel[k] = hb | (0x00040000u + 0x00010001u * k);
+    }
+    const PrepassLane PL = prepass_lane(lane);
+    u32 A = l5 == 0 ? 0u : 0x003F003Fu, B = 0x003F003Fu;
+    u32 acc0 = 0, acc1 = 0;
+    v32u r0, r1;
+
+    // ---- ACS over the blocks, two per trip (the pre-pass's 32 steps) ----
+    {
+        Raw sa = load32(a_off, 0u), sb = load32(b_off, 0u);
+        u32 v = 0;
+        auto rotate = [&](const u32 rbx) {
+            if constexpr (ROT) {
+                switch ((prio_slot + rbx) & 3u) {
+                    case 0: __builtin_amdgcn_s_setprio(0); break;
+                    case 1: __builtin_amdgcn_s_setprio(1); break;
+                    case 2: __builtin_amdgcn_s_setprio(2); break;
+                    default: __builtin_amdgcn_s_setprio(3); break;
+                }
+            }
+        };
+        auto put_reg = [&](const u32 rbx) {
+            u32 i = rbx;
+            asm volatile("" : "+s"(i));  // an index of unknown range: with the constant loop bounds in sight the optimiser turns the insert
+                                         // into a store through a pointer, and the arrays end up in scratch memory instead of VGPRs
+            r0[i] = acc0;  // s_set_gpr_idx_on / v_mov / s_set_gpr_idx_off
+            r1[i] = acc1;
+        };
+        auto put_lds = [&](const u32 rbx) {
+            u32 rbs = rbx;
+            asm volatile("" : "+s"(rbs));  // the address from the scalar block index (see vit_pk_kernel)
+            *reinterpret_cast<uint2*>(dec + (rbs - G::R) * DEC_BLOCK + dslot) = make_uint2(acc1, acc0);
+        };
+        // one trip: table for blocks rb, rb + 1; the next trip's symbols are in flight meanwhile (all inside the frame)
+        auto trip = [&](const u32 rb, auto&& put) {
+            u32 rbs = rb;
+            asm volatile("" : "+s"(rbs));
+            rotate(rb);
+            __syncthreads();
+            prepass(pack_step(sa), pack_step(sb), tab, PL, sel);
+            sa = load32(a_off, rbs + 2u);
+            sb = load32(b_off, rbs + 2u);
+            __syncthreads();
+            steps16<true>(v, A, B, acc0, acc1, tab, L, lane, C);
+            put(rb);
+            v = v == 4 ? 0 : v + 1;
+            rotate(rb + 1u);
+            steps16<true>(v, A, B, acc0, acc1, tab, L1, lane, C);
+            put(rb + 1u);
+            v = v == 4 ? 0 : v + 1;
+        };
+#if VIT_FIC_FIXED_SPLIT
+        for (u32 rb = 0; rb < G::R; rb += 2u) trip(rb, put_reg);
+        for (u32 rb = G::R; rb + 3u < G::NB; rb += 2u) trip(rb, put_lds);
+#else
+        for (u32 rb = 0; rb + 3u < G::NB; rb += 2u)
+            trip(rb, [&](const u32 rbx) {
+                if (rbx < G::R) put_reg(rbx);
+                else put_lds(rbx);
+            });
+#endif
+        // the last pair (static phase): of the 32 steps behind it only the last block's six exist
+        {
+            constexpr u32 rb = G::NB - 3u;
+            rotate(rb);
+            __syncthreads();
+            prepass(pack_step(sa), pack_step(sb), tab, PL, sel);
+            sa = sb = Raw{};
+            if (tau < G::T - (rb + 2u) * 16u) {  // the lanes beyond the frame's end load nothing
+                sa = load32(a_off, rb + 2u);
+                sb = load32(b_off, rb + 2u);
+            }
+            __syncthreads();
+            Steps<rb % 5u, 0, 16, true>::run(A, B, acc0, acc1, tab, L, lane, C);
+            put_lds(rb);
+            rotate(rb + 1u);
+            Steps<(rb + 1u) % 5u, 0, 16, true>::run(A, B, acc0, acc1, tab, L1, lane, C);
+            put_lds(rb + 1u);
+        }
+        {
+            constexpr u32 rb = G::NB - 1u;
+            rotate(rb);
+            __syncthreads();
+            prepass(pack_step(sa), pack_step(sb), tab, PL, sel);
+            __syncthreads();
+            Steps<rb % 5u, 0, 6, true>::run(A, B, acc0, acc1, tab, L, lane, C);
+            acc0 >>= 7;  // see steps6
+            acc1 >>= 7;
+            __syncthreads();  // the last block lands on the table: all reads done first
+            put_lds(rb);
+        }
+    }
+    __syncthreads();
+#ifdef VIT_DIAG_TIMES
+    const unsigned long long diag_t1 = __builtin_amdgcn_s_memrealtime();
+#endif
+    // ---- traceback (fast form only; the image needs no zeroing: every halfword is stored once) ----
+    fixed_traceback<G, G::T, G::R>(dec, img, lane, dslot, r0, r1, P_ZERO, tb16_lane((G::T > 256u + VIT_TAIL ? G::T - 256u : VIT_TAIL) + (lane & 15u) * 16u));
+    __syncthreads();
+#ifdef VIT_DIAG_TIMES
+    if (threadIdx.x == 0 && blockIdx.x < 16384u) {
+        u32 hwid;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+        g_diag_times[blockIdx.x * 4u + 0u] = diag_t0;
+        g_diag_times[blockIdx.x * 4u + 1u] = diag_t1;
+        g_diag_times[blockIdx.x * 4u + 2u] = __builtin_amdgcn_s_memrealtime();
+        g_diag_times[blockIdx.x * 4u + 3u] = hwid;
+    }
+#endif
+    // ---- output: bit b of the image is decoded bit b, bytes are MSB-first; sixteen lanes per frame, dword stores ----
+    {
+        const u32 k = lane >> 4, j = lane & 15u;
+        if (k < nvalid) {
+            u32* o = reinterpret_cast<u32*>(gout + k * G::OUT_BYTES);
+            const u32* im = img + k * G::FSTRIDE;
+#pragma unroll
+            for (u32 m0 = 0; m0 < G::FSTRIDE; m0 += 16u)
+                if (m0 + 16u <= G::FSTRIDE || j < G::FSTRIDE - m0) o[m0 + j] = __builtin_bswap32(__builtin_bitreverse32(im[m0 + j]));
         }
     }
 }
@@ -1602,6 +1892,24 @@ hipError_t vit_launch_pk(const void* d_symbols, bool sym32, uint8_t* d_out, cons
         if (per_cu > 16u) per_cu = 16u;  // 4 waves per SIMD (launch bounds)
         // (a launch of at most one wave per SIMD has nothing to rotate between, and the s_setprio per block costs it time)
         const bool rot = may_rotate && g <= (long long)per_cu * vit_device_cus(dev) && g > 4ll * vit_device_cus(dev);
+#if VIT_FIC_FIXED
+        // a uniform batch of FIC frames (no descriptor table, not the gated second launch of a split table): the fixed-geometry
+        // instantiation, static LDS.  Forced or chosen, the packed kernel gets here either way.
+        if (!d_desc && !gate && framebits == 768u && l.maxfb == 768u) {
+#define VIT_LAUNCH_FIXED(S32, R)                                                                                          \
+    hipLaunchKernelGGL((vit_pk_fixed_kernel<768u, S32, R>), dim3((unsigned)g), dim3(64), 0, stream, d_sym, d_out, \
+                       (long long)nframes, rc)
+            if (sym32) {
+                if (rot) VIT_LAUNCH_FIXED(true, true);
+                else VIT_LAUNCH_FIXED(true, false);
+            } else {
+                if (rot) VIT_LAUNCH_FIXED(false, true);
+                else VIT_LAUNCH_FIXED(false, false);
+            }
+#undef VIT_LAUNCH_FIXED
+            return;
+        }
+#endif
 #define VIT_LAUNCH_SHORT(S32, R)                                                                                          \
     hipLaunchKernelGGL((vit_pk_kernel<S32, R>), dim3((unsigned)g), dim3(64), l.total, stream, d_sym, d_out, d_desc, framebits, \
                        (long long)nframes, l, vmax, gate, rc)
