@@ -187,17 +187,19 @@ DEV void acs_step(u32& A, u32& B, u32& acc0, u32& acc1, u32 mt, u32 lane, const 
     // sign(m0-m1) = 1  <=>  m0 < m1  <=>  decision bit 0 (tie -> decision 1)
     if constexpr (HIST) {
         const us2 x01 = m0 - m1, x23 = m2 - m3;
-        // history: |m0 - m1| <= 255, so bits 9..15 of each half of the difference are seven copies
-        // of its sign, and one v_bfi can drop the decision at any of those positions.  Step j of
-        // the block ends up at bit j of its half with only TWO 32-bit shifts per 16 steps:
-        //   steps 0,1 -> bits 14,15 | >>7 | steps 2..8 -> bits 9..15 | >>7 | steps 9..15 -> bits 9..15
-        // (what a shift carries from the upper half into bits 9..15 is overwritten by the seven
-        // inserts that follow it; the stale bits of the previous block are shifted out).
-        constexpr int pos = J < 2 ? 14 + J : J < 9 ? 7 + J : J;
+        // history: both metrics carry the same bias and lie in one 256-wide range, so m0 - m1 is in
+        // [-255, 255] (0xFF01 .. 0x00FF) and bits 8..15 of each half of the difference are EIGHT
+        // copies of its sign: one v_bfi can drop the decision at any of those positions.
+        // Step j of the block ends up at bit j of its half with ONE 32-bit shift per 16 steps:
+        //   steps 0..7 -> bits 8..15 | >>8 | steps 8..15 -> bits 8..15
+        // (what the shift carries from the upper half into bits 8..15 of the lower one is overwritten
+        // by the eight inserts that follow it; the stale bits of the previous block are overwritten by
+        // the first eight inserts or shifted out).
+        constexpr int pos = 8 + (J & 7);
         constexpr u32 mask = 0x00010001u << pos;
-        if constexpr (J == 2 || J == 9) {
-            acc0 >>= 7;
-            acc1 >>= 7;
+        if constexpr (J == 8) {
+            acc0 >>= 8;
+            acc1 >>= 8;
         }
         acc0 = bfi(mask, W(x01), acc0);
         acc1 = bfi(mask, W(x23), acc1);
@@ -291,12 +293,12 @@ DEV void steps16(u32 v, u32& A, u32& B, u32& acc0, u32& acc1, const char* th, co
     }
 }
 // Last block of a frame whose step count is 6 mod 16 - every DAB size (framebits = 96*m, and the FIC's
-// 768): the ten padding steps are not computed.  After six steps the history sits at bits 7..12 of
+// 768): the ten padding steps are not computed.  After six steps the history sits at bits 8..13 of
 // each half (see acs_step); one more shift puts step j at bit j like in a full block.
 DEV void steps6(u32 v, u32& A, u32& B, u32& acc0, u32& acc1, const char* th, const Lanes& L, u32 lane, const Consts& C) {
     steps16<true, 6>(v, A, B, acc0, acc1, th, L, lane, C);
-    acc0 >>= 7;
-    acc1 >>= 7;
+    acc0 >>= 8;
+    acc1 >>= 8;
 }
 
 typedef u32 v32u __attribute__((ext_vector_type(32)));
@@ -1048,7 +1050,11 @@ __global__ __launch_bounds__(64, 4) void vit_pk_fixed_kernel(const uint8_t* __re
     const u32 lane = threadIdx.x;
     u32 prio_slot = 0;
 #if VIT_PRIO
-    {  // one wave of the four of a SIMD at low priority (see vit_pk_kernel)
+    // Static priorities (one wave of a SIMD low, see vit_pk_kernel) only where they rotate.  In a launch of several rounds this
+    // kernel runs without any: with them the low-priority wave of a SIMD outlives its neighbours and what is left of it when the
+    // dispatcher runs dry finishes alone - a drain of 29 to 48 us whose length swings with a 1 % change of a wave's instruction
+    // count, and which cost the no-signal inputs 3-5 % (profiles/r10_fic_isa_ab.txt).
+    if constexpr (ROT) {
         u32 hwid;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
         prio_slot = hwid & 3u;
@@ -1082,6 +1088,7 @@ __global__ __launch_bounds__(64, 4) void vit_pk_fixed_kernel(const uint8_t* __re
 #pragma unroll
         for (int rho = 0; rho < 5; rho++) {
             L.toff[rho] += tb;
+            asm volatile("" : "+v"(L.toff[rho]));  // tb is a constant here (static LDS): without this the sum is redone in front of every table read
             L1.toff[rho] = L.toff[rho] + 1024u;
             asm volatile("" : "+v"(L1.toff[rho]));
         }
@@ -1193,8 +1200,8 @@ __global__ __launch_bounds__(64, 4) void vit_pk_fixed_kernel(const uint8_t* __re
             prepass(pack_step(sa), pack_step(sb), tab, PL, sel);
             __syncthreads();
             Steps<rb % 5u, 0, 6, true>::run(A, B, acc0, acc1, tab, L, lane, C);
-            acc0 >>= 7;  // see steps6
-            acc1 >>= 7;
+            acc0 >>= 8;  // see steps6
+            acc1 >>= 8;
             __syncthreads();  // the last block lands on the table: all reads done first
             put_lds(rb);
         }
