@@ -381,6 +381,76 @@ int vit_ofdm_demap_dev(const float *d_fft, uint64_t sym_stride, uint64_t frame_s
                        const vit_ofdm_shape *shape, float gain, int64_t nframes, uint8_t *d_fic,
                        const vit_cif_ring *ring, uint64_t col, void *stream);
 
+/* From the samples: fine-frequency correction, the FFT of every OFDM symbol and, fused behind it, exactly what
+ * vit_ofdm_demap_dev does - the step between baseband samples on the device and vit_decode_fic_dev / the ring, with no
+ * spectrum written to memory and no third-party FFT in the caller's hot path.  Like the demapper it is defined bit for bit.
+ * Input: a HOST struct, read during the call (like vit_cif_ring).  A frame's "start" is the first useful sample of its
+ * phase reference symbol (the caller places it inside the guard interval as its time synchronisation says); the useful
+ * part of symbol l of frame t is samples start_t + l*sym_stride ... + nfft - 1.  Nothing else is read: not the samples
+ * between useful parts, not the null symbol.  Any sample position is allowed; only d_iq must be 8-byte aligned.
+ * Out of scope: time and frequency estimation, integer sample formats, resampling, channel-state weighting. */
+typedef struct vit_iq_input {
+    const float    *d_iq;         /* interleaved (re, im) float32 samples, 8-byte aligned */
+    uint64_t        nsamples;     /* complex samples in d_iq: nothing at or beyond it is read */
+    uint64_t        sym_stride;   /* samples from one symbol's useful part to the next: nfft + guard (mode I 2552), >= nfft */
+    uint64_t        frame_stride; /* frame t starts at sample t*frame_stride when d_start is NULL (mode I 196608) */
+    const int64_t  *d_start;      /* optional DEVICE table: frame t starts at sample d_start[t] (timing re-estimated per frame) */
+    const float    *d_tw;         /* DEVICE: nfft/2 twiddles, from vit_fft_twiddles */
+    const float    *d_nco;        /* optional DEVICE: 2^nco_bits phasors, from vit_nco_table */
+    uint32_t        nco_bits;     /* 1 ... 20 */
+    const uint32_t *d_rot;        /* optional DEVICE: per frame {phase0, step}; NULL = no rotation, not even by 1 */
+} vit_iq_input;
+/* Definition.  Every operation is one IEEE binary32 operation, rounded to nearest-even, in exactly this order, never
+ * contracted into an FMA; tw and nco are the caller's tables (the builders below give the intended ones).
+ * 1. Rotation, only if d_rot is given.  Sample n of a frame is counted from the frame's start, guards included:
+ *    n = l*sym_stride + i for sample i of symbol l, so the phase is continuous across the frame.  With
+ *    w = nco[((phase0 + n*step) mod 2^32) >> (32 - nco_bits)]:
+ *      x'.re = fl(fl(x.re*w.re) - fl(x.im*w.im))
+ *      x'.im = fl(fl(x.re*w.im) + fl(x.im*w.re))
+ *    The caller sets step = round(-df/fs * 2^32) mod 2^32 for a frequency offset df at sample rate fs.
+ * 2. FFT, nfft = 2^m: radix-2 decimation in time.  x0[i] = x'[bitrev_m(i)].  For stage s = 1 ... m, with h = 2^(s-1),
+ *    for every block base i (a multiple of 2^s) and j < h:
+ *      w = tw[j * (nfft >> s)],  u = x[i+j],  v = x[i+j+h]
+ *      t.re = fl(fl(w.re*v.re) - fl(w.im*v.im))
+ *      t.im = fl(fl(w.re*v.im) + fl(w.im*v.re))
+ *      x[i+j] = u + t,  x[i+j+h] = u - t            component by component
+ *    The result is X[k] in FFT order: bin 0 = DC, carrier k < 0 at bin nfft + k.
+ *    This pins the arithmetic graph, not an implementation: any grouping of stages and any memory layout compute the same
+ *    bits as long as the same butterflies meet the same twiddles.
+ * 3. Demapping (vit_ofdm_demod_dev): the definition of vit_ofdm_demap_dev unchanged, with z = X.
+ * Domain: the result is defined for samples that are 0 or have a magnitude in [2^-40, 2^40].  There no
+ * product with a table entry is denormal and nothing overflows before the demapper, whose own rules then take care of
+ * Inf.  For a symbol that holds anything else (NaN, Inf, denormals, larger magnitudes) the outputs of that symbol and of
+ * the next are unspecified; nothing is written outside the call's output bytes.  (So an implementation may skip the
+ * multiplications by the exact table entries 1 and -j.)  The sign of a zero influences no output byte; spectra are
+ * defined by value (-0 = +0).
+ * Tables, host only, need no GPU (like vit_freq_interleave_bins).  Both compute in binary64 and round to binary32, except
+ * that entries at multiples of an eighth of a turn are exact: 0, +-1, +-fl(sqrt(1/2)).  Each returns the number of pairs
+ * written, or -1 for a NULL pointer or an argument out of range.
+ *   vit_fft_twiddles: nfft/2 pairs (cos, -sin)(2 pi k / nfft), nfft a power of two 64 ... 8192
+ *   vit_nco_table:    2^nco_bits pairs (cos, +sin)(2 pi k / 2^nco_bits), nco_bits 1 ... 20 */
+int64_t vit_fft_twiddles(uint32_t nfft, float *h_tw);
+int64_t vit_nco_table(uint32_t nco_bits, float *h_nco);
+/* vit_ofdm_fft_dev: steps 1 and 2 for symbols 0 ... nsyms-1 of nframes frames; X of symbol l of frame t goes to complex
+ * elements t*out_frame_stride + l*out_sym_stride ... + nfft - 1 of d_fft, the layout vit_ofdm_demap_dev reads (d_fft
+ * 16-byte aligned, both output strides even, out_sym_stride >= nfft); nothing else of d_fft is written.  For callers
+ * that need a spectrum (the phase reference symbol for synchronisation, a channel estimate).
+ * vit_ofdm_demod_dev: steps 1 to 3; d_bins, shape, gain, d_fic, ring and col as in vit_ofdm_demap_dev, with the same
+ * destinations, rules and guarantees (no write outside the named bytes, other ring rows untouched, no bin that d_bins
+ * does not name influences any output).
+ * Argument rules as the other *_dev calls: VIT_ERR_NO_DEVICE first; VIT_ERR_ARG (with vit_last_error()) for a NULL `in`,
+ * d_iq, d_tw or output, a d_iq, d_tw, d_nco, d_start or d_rot that is not 8-byte aligned, sym_stride < nfft, nfft not a power of two 64 ... 8192, nsyms = 0, d_rot
+ * without d_nco or with nco_bits outside 1 ... 20, nframes < 0, and every rule of vit_ofdm_demap_dev for the outputs.
+ * A frame's reads are taken to span all its symbols, start ... start + (nsyms-1)*sym_stride + nfft - 1, whichever of
+ * them the call needs.  With d_start == NULL a last frame that would read beyond nsamples is VIT_ERR_ARG.  With d_start
+ * given, a frame whose reads would fall outside [0, nsamples) is skipped on the device: every output byte of that
+ * frame keeps its old value (the rule vit_decode_varlen_dev_checked has for its table).  An empty batch returns VIT_OK
+ * and writes nothing; everything is enqueued on `stream` without synchronising. */
+int vit_ofdm_fft_dev(const vit_iq_input *in, uint32_t nfft, uint32_t nsyms, int64_t nframes, float *d_fft,
+                     uint64_t out_sym_stride, uint64_t out_frame_stride, void *stream);
+int vit_ofdm_demod_dev(const vit_iq_input *in, const uint16_t *d_bins, const vit_ofdm_shape *shape, float gain,
+                       int64_t nframes, uint8_t *d_fic, const vit_cif_ring *ring, uint64_t col, void *stream);
+
 /* Kernel selection (the analogue of the reference's dispatcher, setupdll.cpp:195-270):
  *   0 = auto: launches of up to 2048 frames (they cannot fill the chip) take the latency kernel - one
  *       frame per wavefront, ~20 us per FIC frame -, larger ones the packed throughput kernel;

@@ -30,6 +30,7 @@ EXPORTS = [
     "vit_decode_fic_dev", "vit_dabplus_punctured_superframes_dev",
     "vit_time_deinterleave_dev", "vit_decode_punctured_ti_dev", "vit_dabplus_ti_superframes_dev",
     "vit_freq_interleave_bins", "vit_ofdm_demap_dev",
+    "vit_fft_twiddles", "vit_nco_table", "vit_ofdm_fft_dev", "vit_ofdm_demod_dev",
     "vit_decode_stream_multi",
 ]
 MULTI_LOOPBACK = 0x1
@@ -69,6 +70,13 @@ class OfdmShape(C.Structure):
     """vit_ofdm_shape of include/viterbi_amd.h: OfdmShape(nfft, ncarriers, nsyms, fic_syms, cifs)"""
     _fields_ = [("nfft", C.c_uint32), ("ncarriers", C.c_uint32), ("nsyms", C.c_uint32), ("fic_syms", C.c_uint32),
                 ("cifs", C.c_uint32)]
+
+
+class IqInput(C.Structure):
+    """vit_iq_input of include/viterbi_amd.h: baseband samples on the device and the tables of the front end"""
+    _fields_ = [("d_iq", C.c_void_p), ("nsamples", C.c_uint64), ("sym_stride", C.c_uint64), ("frame_stride", C.c_uint64),
+                ("d_start", C.c_void_p), ("d_tw", C.c_void_p), ("d_nco", C.c_void_p), ("nco_bits", C.c_uint32),
+                ("d_rot", C.c_void_p)]
 
 
 # the four transmission modes of EN 300 401 as shapes (examples: the library compiles in no table of modes)
@@ -141,6 +149,13 @@ def lib():
         L.vit_freq_interleave_bins.restype = C.c_int64
         L.vit_ofdm_demap_dev.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.POINTER(OfdmShape), C.c_float, C.c_int64, vp, pr,
                                          C.c_uint64, vp]
+        pi = C.POINTER(IqInput)
+        L.vit_fft_twiddles.argtypes = [C.c_uint32, vp]
+        L.vit_fft_twiddles.restype = C.c_int64
+        L.vit_nco_table.argtypes = [C.c_uint32, vp]
+        L.vit_nco_table.restype = C.c_int64
+        L.vit_ofdm_fft_dev.argtypes = [pi, C.c_uint32, C.c_uint32, C.c_int64, vp, C.c_uint64, C.c_uint64, vp]
+        L.vit_ofdm_demod_dev.argtypes = [pi, vp, C.POINTER(OfdmShape), C.c_float, C.c_int64, vp, pr, C.c_uint64, vp]
         _lib = L
     return _lib
 
@@ -486,6 +501,91 @@ def ofdm_demap_dev(d_fft, shape, d_bins, gain, nframes, d_fic=None, d_ring=None,
     ring = None if d_ring is None else C.byref(cif_ring(d_ring, first_row))
     _check(lib().vit_ofdm_demap_dev(_ptr(d_fft), sym_stride, frame_stride, _ptr(d_bins), C.byref(shape), float(gain), nframes,
                                     _ptr(d_fic), ring, col, _stream_ptr(stream)), "vit_ofdm_demap_dev")
+
+
+def fft_twiddles(nfft):
+    """the FFT's twiddles (include/viterbi_amd.h, "From the samples"): nfft/2 pairs (cos, -sin)(2 pi k / nfft) -> float32
+    numpy array (nfft/2, 2); ValueError unless nfft is a power of two 64 ... 8192 (host only, needs no GPU)"""
+    out = np.zeros((4096, 2), np.float32)
+    n = lib().vit_fft_twiddles(int(nfft) & 0xFFFFFFFF, _np(out))
+    if n < 0:
+        raise ValueError("nfft must be a power of two 64 ... 8192: %r" % (nfft,))
+    return out[:n].copy()
+
+
+def nco_table(bits):
+    """the phasors of the fine-frequency rotation: 2^bits pairs (cos, +sin)(2 pi k / 2^bits) -> float32 numpy array
+    (2^bits, 2); ValueError unless 1 <= bits <= 20 (host only, needs no GPU)"""
+    if not 1 <= int(bits) <= 20:
+        raise ValueError("bits must be 1 ... 20: %r" % (bits,))
+    out = np.zeros((1 << int(bits), 2), np.float32)
+    n = lib().vit_nco_table(int(bits), _np(out))
+    if n != out.shape[0]:
+        raise ValueError("bits must be 1 ... 20: %r" % (bits,))
+    return out
+
+
+def iq_input(d_iq, d_tw, sym_stride, frame_stride=0, d_start=None, d_nco=None, nco_bits=0, d_rot=None, nsamples=None):
+    """device tensors -> IqInput.  d_iq: complex64 or (re, im)-interleaved float32 CUDA tensor; d_tw / d_nco: float32 CUDA
+    tensors from fft_twiddles / nco_table; d_start: int64 CUDA tensor of frame starts; d_rot: CUDA tensor of 4-byte
+    elements, {phase0, step} per frame (torch has no uint32 arithmetic: upload a numpy uint32 array viewed as int32).
+    nsamples defaults to all of d_iq."""
+    if not d_iq.is_cuda or str(d_iq.dtype) not in ("torch.complex64", "torch.float32"):
+        raise ValueError("d_iq must be a complex64 or float32 CUDA tensor")
+    if not d_tw.is_cuda or str(d_tw.dtype) != "torch.float32" or (d_nco is not None and str(d_nco.dtype) != "torch.float32"):
+        raise ValueError("d_tw and d_nco must be float32 CUDA tensors")
+    if d_start is not None and (not d_start.is_cuda or str(d_start.dtype) != "torch.int64"):
+        raise ValueError("d_start must be an int64 CUDA tensor")
+    if d_rot is not None and (not d_rot.is_cuda or d_rot.element_size() != 4):
+        raise ValueError("d_rot must be a CUDA tensor of 4-byte elements (uint32 pairs)")
+    total = d_iq.numel() if str(d_iq.dtype) == "torch.complex64" else d_iq.numel() // 2
+    a = IqInput()
+    a.d_iq = d_iq.data_ptr()
+    a.nsamples = total if nsamples is None else int(nsamples)
+    a.sym_stride = int(sym_stride)
+    a.frame_stride = int(frame_stride or 0)
+    a.d_start = None if d_start is None else d_start.data_ptr()
+    a.d_tw = d_tw.data_ptr()
+    a.d_nco = None if d_nco is None else d_nco.data_ptr()
+    a.nco_bits = int(nco_bits)
+    a.d_rot = None if d_rot is None else d_rot.data_ptr()
+    return a
+
+
+def ofdm_fft_dev(d_iq, nfft, nsyms, nframes, d_tw, sym_stride, d_fft, frame_stride=None, d_start=None, d_nco=None,
+                 nco_bits=0, d_rot=None, out_sym_stride=None, out_frame_stride=None, stream=None, nsamples=None):
+    """From the samples (include/viterbi_amd.h): rotation and FFT of symbols 0 ... nsyms-1 of nframes frames into d_fft
+    (complex64 or float32 CUDA tensor) in the layout ofdm_demap_dev reads.  Input arguments as iq_input; frame_stride is
+    required unless d_start is given; the output strides count complex elements and default to nfft and
+    nsyms*out_sym_stride."""
+    if not d_fft.is_cuda or str(d_fft.dtype) not in ("torch.complex64", "torch.float32"):
+        raise ValueError("d_fft must be a complex64 or float32 CUDA tensor")
+    if frame_stride is None and d_start is None:
+        raise ValueError("frame_stride or d_start is required")
+    inp = iq_input(d_iq, d_tw, sym_stride, frame_stride, d_start, d_nco, nco_bits, d_rot, nsamples)
+    if out_sym_stride is None:
+        out_sym_stride = int(nfft)
+    if out_frame_stride is None:
+        out_frame_stride = int(nsyms) * out_sym_stride
+    _check(lib().vit_ofdm_fft_dev(C.byref(inp), int(nfft), int(nsyms), nframes, _ptr(d_fft), out_sym_stride, out_frame_stride,
+                                  _stream_ptr(stream)), "vit_ofdm_fft_dev")
+
+
+def ofdm_demod_dev(d_iq, shape, d_bins, gain, nframes, d_tw, sym_stride, frame_stride=None, d_start=None, d_nco=None,
+                   nco_bits=0, d_rot=None, d_fic=None, d_ring=None, first_row=0, col=0, stream=None, nsamples=None):
+    """From the samples (include/viterbi_amd.h): rotation, FFT and the demapping of ofdm_demap_dev in one kernel, no spectrum
+    in memory.  Input arguments as iq_input (frame_stride is required unless d_start is given); shape, d_bins, gain,
+    d_fic, d_ring, first_row and col as ofdm_demap_dev."""
+    if not isinstance(shape, OfdmShape):
+        shape = OfdmShape(*[int(v) for v in shape])
+    if not d_bins.is_cuda or d_bins.element_size() != 2:
+        raise ValueError("d_bins must be a CUDA tensor of 2-byte elements (uint16 bins)")
+    if frame_stride is None and d_start is None:
+        raise ValueError("frame_stride or d_start is required")
+    inp = iq_input(d_iq, d_tw, sym_stride, frame_stride, d_start, d_nco, nco_bits, d_rot, nsamples)
+    ring = None if d_ring is None else C.byref(cif_ring(d_ring, first_row))
+    _check(lib().vit_ofdm_demod_dev(C.byref(inp), _ptr(d_bins), C.byref(shape), float(gain), nframes, _ptr(d_fic), ring, col,
+                                    _stream_ptr(stream)), "vit_ofdm_demod_dev")
 
 
 def decode_stream_multi(d_symbols_u8, d_out, framebits, nframes, devices, chunk_frames, root_frames=-1, flags=0,

@@ -1247,15 +1247,9 @@ int64_t vit_freq_interleave_bins(uint32_t nfft, uint16_t* h_bins) {
     return n;
 }
 
-int vit_ofdm_demap_dev(const float* d_fft, uint64_t sym_stride, uint64_t frame_stride, const uint16_t* d_bins,
-                       const vit_ofdm_shape* shape, float gain, int64_t nframes, uint8_t* d_fic, const vit_cif_ring* ring,
-                       uint64_t col, void* stream) {
-    const char* who = "vit_ofdm_demap_dev";
-    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
-    if (!d_fft || !d_bins || !shape || nframes < 0) {
-        set_err("%s: bad arguments (NULL d_fft, d_bins or shape, or nframes=%lld < 0)", who, (long long)nframes);
-        return VIT_ERR_ARG;
-    }
+// the rules of vit_ofdm_demap_dev for where the soft bytes go and what they are made from (shared with vit_ofdm_demod_dev)
+static int ofdm_check_outputs(const char* who, const vit_ofdm_shape* shape, float gain, int64_t nframes, const uint8_t* d_fic,
+                              const vit_cif_ring* ring, uint64_t col) {
     if (!d_fic && !ring) {
         set_err("%s: bad arguments (d_fic and ring both NULL)", who);
         return VIT_ERR_ARG;
@@ -1269,11 +1263,6 @@ int vit_ofdm_demap_dev(const float* d_fft, uint64_t sym_stride, uint64_t frame_s
     }
     if (!(gain > 0.0f && gain <= 65536.0f)) {  // false for NaN
         set_err("%s: bad arguments (gain %g, 0 < gain <= 65536)", who, (double)gain);
-        return VIT_ERR_ARG;
-    }
-    if (((uintptr_t)d_fft & 15u) != 0 || (sym_stride & 1u) != 0 || (frame_stride & 1u) != 0 || sym_stride < sh.nfft) {
-        set_err("%s: bad arguments (d_fft must be 16-byte aligned, sym_stride %llu and frame_stride %llu even, sym_stride >= "
-                "nfft)", who, (unsigned long long)sym_stride, (unsigned long long)frame_stride);
         return VIT_ERR_ARG;
     }
     if (ring) {
@@ -1297,10 +1286,112 @@ int vit_ofdm_demap_dev(const float* d_fft, uint64_t sym_stride, uint64_t frame_s
             return VIT_ERR_ARG;
         }
     }
+    return VIT_OK;
+}
+
+int vit_ofdm_demap_dev(const float* d_fft, uint64_t sym_stride, uint64_t frame_stride, const uint16_t* d_bins,
+                       const vit_ofdm_shape* shape, float gain, int64_t nframes, uint8_t* d_fic, const vit_cif_ring* ring,
+                       uint64_t col, void* stream) {
+    const char* who = "vit_ofdm_demap_dev";
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (!d_fft || !d_bins || !shape || nframes < 0) {
+        set_err("%s: bad arguments (NULL d_fft, d_bins or shape, or nframes=%lld < 0)", who, (long long)nframes);
+        return VIT_ERR_ARG;
+    }
+    const vit_ofdm_shape& sh = *shape;
+    if (ofdm_check_outputs(who, shape, gain, nframes, d_fic, ring, col) != VIT_OK) return VIT_ERR_ARG;
+    if (((uintptr_t)d_fft & 15u) != 0 || (sym_stride & 1u) != 0 || (frame_stride & 1u) != 0 || sym_stride < sh.nfft) {
+        set_err("%s: bad arguments (d_fft must be 16-byte aligned, sym_stride %llu and frame_stride %llu even, sym_stride >= "
+                "nfft)", who, (unsigned long long)sym_stride, (unsigned long long)frame_stride);
+        return VIT_ERR_ARG;
+    }
     if (nframes == 0) return VIT_OK;
     hipError_t e = vit_launch_ofdm_demap(d_fft, sym_stride, frame_stride, d_bins, sh, gain, nframes, d_fic, ring, col,
                                          (hipStream_t)stream);
     if (e != hipSuccess) { set_err("OFDM demap launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
+    return VIT_OK;
+}
+
+// ---- from the samples: rotation, FFT and the demapping behind it (vit_ofdm_td.hip) --------------------------------------
+int64_t vit_fft_twiddles(uint32_t nfft, float* h_tw) {
+    const int64_t n = vit_fft_twiddles_host(nfft, h_tw);
+    if (n < 0) set_err("vit_fft_twiddles: bad arguments (nfft=%u, a power of two 64 ... 8192)", nfft);
+    return n;
+}
+
+int64_t vit_nco_table(uint32_t nco_bits, float* h_nco) {
+    const int64_t n = vit_nco_table_host(nco_bits, h_nco);
+    if (n < 0) set_err("vit_nco_table: bad arguments (nco_bits=%u, 1 ... 20)", nco_bits);
+    return n;
+}
+
+// the rules of vit_iq_input for frames of nsyms symbols of nfft samples (nfft already checked)
+static int ofdm_check_input(const char* who, const vit_iq_input* in, uint32_t nfft, uint32_t nsyms, int64_t nframes) {
+    if (!in || !in->d_iq || !in->d_tw || nframes < 0) {
+        set_err("%s: bad arguments (NULL in, d_iq or d_tw, or nframes=%lld < 0)", who, (long long)nframes);
+        return VIT_ERR_ARG;
+    }
+    if (((uintptr_t)in->d_iq & 7u) != 0 || ((uintptr_t)in->d_tw & 7u) != 0 || ((uintptr_t)in->d_nco & 7u) != 0 ||
+        ((uintptr_t)in->d_start & 7u) != 0 || ((uintptr_t)in->d_rot & 7u) != 0) {
+        set_err("%s: bad arguments (d_iq, d_tw, d_nco, d_start and d_rot must be 8-byte aligned)", who);
+        return VIT_ERR_ARG;
+    }
+    if (in->d_rot && (!in->d_nco || in->nco_bits < 1u || in->nco_bits > 20u)) {
+        set_err("%s: bad arguments (d_rot needs d_nco and nco_bits 1 ... 20, got %u)", who, in->nco_bits);
+        return VIT_ERR_ARG;
+    }
+    // a frame's reads: start ... start + (nsyms-1)*sym_stride + nfft - 1
+    const unsigned __int128 extent = (unsigned __int128)(nsyms - 1u) * in->sym_stride + nfft;
+    if (in->sym_stride < nfft || extent > (unsigned __int128)UINT64_MAX) {
+        set_err("%s: bad arguments (sym_stride %llu, >= nfft %u and a frame within 2^64 samples)", who,
+                (unsigned long long)in->sym_stride, nfft);
+        return VIT_ERR_ARG;
+    }
+    if (!in->d_start && nframes > 0) {
+        const unsigned __int128 end = (unsigned __int128)(uint64_t)(nframes - 1) * in->frame_stride + extent;
+        if (end > (unsigned __int128)in->nsamples) {
+            set_err("%s: bad arguments (%lld frames at frame_stride %llu read beyond nsamples %llu)", who, (long long)nframes,
+                    (unsigned long long)in->frame_stride, (unsigned long long)in->nsamples);
+            return VIT_ERR_ARG;
+        }
+    }
+    return VIT_OK;
+}
+
+int vit_ofdm_fft_dev(const vit_iq_input* in, uint32_t nfft, uint32_t nsyms, int64_t nframes, float* d_fft,
+                     uint64_t out_sym_stride, uint64_t out_frame_stride, void* stream) {
+    const char* who = "vit_ofdm_fft_dev";
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (nfft < 64u || nfft > 8192u || (nfft & (nfft - 1u)) != 0 || nsyms == 0) {
+        set_err("%s: bad arguments (nfft=%u, a power of two 64 ... 8192; nsyms=%u > 0)", who, nfft, nsyms);
+        return VIT_ERR_ARG;
+    }
+    if (!d_fft || ((uintptr_t)d_fft & 15u) != 0 || (out_sym_stride & 1u) != 0 || (out_frame_stride & 1u) != 0 ||
+        out_sym_stride < nfft) {
+        set_err("%s: bad arguments (d_fft must be non-NULL and 16-byte aligned, out_sym_stride %llu and out_frame_stride %llu "
+                "even, out_sym_stride >= nfft)", who, (unsigned long long)out_sym_stride, (unsigned long long)out_frame_stride);
+        return VIT_ERR_ARG;
+    }
+    if (ofdm_check_input(who, in, nfft, nsyms, nframes) != VIT_OK) return VIT_ERR_ARG;
+    if (nframes == 0) return VIT_OK;
+    hipError_t e = vit_launch_ofdm_fft(*in, nfft, nsyms, nframes, d_fft, out_sym_stride, out_frame_stride, (hipStream_t)stream);
+    if (e != hipSuccess) { set_err("OFDM FFT launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
+    return VIT_OK;
+}
+
+int vit_ofdm_demod_dev(const vit_iq_input* in, const uint16_t* d_bins, const vit_ofdm_shape* shape, float gain, int64_t nframes,
+                       uint8_t* d_fic, const vit_cif_ring* ring, uint64_t col, void* stream) {
+    const char* who = "vit_ofdm_demod_dev";
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (!d_bins || !shape || nframes < 0) {
+        set_err("%s: bad arguments (NULL d_bins or shape, or nframes=%lld < 0)", who, (long long)nframes);
+        return VIT_ERR_ARG;
+    }
+    if (ofdm_check_outputs(who, shape, gain, nframes, d_fic, ring, col) != VIT_OK) return VIT_ERR_ARG;
+    if (ofdm_check_input(who, in, shape->nfft, shape->nsyms, nframes) != VIT_OK) return VIT_ERR_ARG;
+    if (nframes == 0) return VIT_OK;
+    hipError_t e = vit_launch_ofdm_demod(*in, d_bins, *shape, gain, nframes, d_fic, ring, col, (hipStream_t)stream);
+    if (e != hipSuccess) { set_err("OFDM demodulation launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
     return VIT_OK;
 }
 

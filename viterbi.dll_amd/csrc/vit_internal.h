@@ -97,6 +97,15 @@ int64_t vit_freq_bins_host(uint32_t nfft, uint16_t* h_bins);
 hipError_t vit_launch_ofdm_demap(const float* d_fft, uint64_t sym_stride, uint64_t frame_stride, const uint16_t* d_bins,
                                  const vit_ofdm_shape& shape, float gain, int64_t nframes, uint8_t* d_fic,
                                  const vit_cif_ring* ring, uint64_t col, hipStream_t stream);
+// From the samples (vit_ofdm_td.hip).  The tables of include/viterbi_amd.h: pairs written, or -1.
+int64_t vit_fft_twiddles_host(uint32_t nfft, float* h_tw);
+int64_t vit_nco_table_host(uint32_t nco_bits, float* h_nco);
+// Rotation and FFT of nframes frames, then the spectra to d_fft (vit_launch_ofdm_fft) or the demapping of
+// vit_launch_ofdm_demap without a spectrum in memory (vit_launch_ofdm_demod); the caller has checked every argument rule.
+hipError_t vit_launch_ofdm_fft(const vit_iq_input& in, uint32_t nfft, uint32_t nsyms, int64_t nframes, float* d_fft,
+                               uint64_t out_sym_stride, uint64_t out_frame_stride, hipStream_t stream);
+hipError_t vit_launch_ofdm_demod(const vit_iq_input& in, const uint16_t* d_bins, const vit_ofdm_shape& shape, float gain,
+                                 int64_t nframes, uint8_t* d_fic, const vit_cif_ring* ring, uint64_t col, hipStream_t stream);
 // After the decoder (vit_dab.hip).  The energy dispersal PRBS of one frame, (framebits+7)/8 bytes, padding bits 0
 // (framebits even, <= 9216; the caller checks).
 int64_t vit_prbs_bytes_host(uint8_t* h_out, uint32_t framebits);

@@ -1,0 +1,458 @@
+// vit_ofdm_td.hip -- from the samples to soft bytes (include/viterbi_amd.h, "From the samples"): fine-frequency rotation,
+// the FFT of every OFDM symbol and, fused behind it, exactly the demapping of vit_ofdm.hip - no spectrum goes through
+// memory (vit_ofdm_demod_dev) - or the spectra themselves in the layout vit_ofdm_demap_dev reads (vit_ofdm_fft_dev).
+//
+// The result is defined bit for bit: every float operation is one IEEE binary32 operation (contraction off, plain
+// operators), the butterflies are the header's radix-2 decimation-in-time graph with the header's twiddles.  Only the
+// multiplications by the exact twiddles 1 and -j of stages 1 and 2 are skipped (the header's domain makes that free).
+//
+// One workgroup owns one frame and a run of consecutive symbols; a symbol's FFT lives in LDS as nfft padded float2.
+// A thread owns 8 points of every pass (nfft/8 threads work on a symbol; at nfft < 512 the rest of the 64 idle in the
+// FFT).  The stages are grouped into passes of 3 (radix-8 in registers), preceded by one pass of m mod 3 stages:
+//   first pass   straight from the sample registers: thread T holds samples T + c*nfft/R, which bit reversal makes the
+//                R consecutive points of group bitrev(T); rotation, stages 1 ... log2 R, one LDS store per point;
+//   other passes 8 LDS loads at stride 2^s, 3 stages, 8 LDS stores in place, a barrier.
+// The twiddle table is copied to LDS behind the symbol once per workgroup and a thread loads its 7 twiddles per radix-8
+// pass from there: they are the same for every symbol, but kept in registers (21 float2 at nfft 2048) they cost a
+// wavefront per SIMD, which costs more than the loads.  The next symbol's samples (and phasors) are loaded right after
+// the first pass has consumed this symbol's: they are in flight during the other passes, the barriers and the outputs.
+// Demapping: carrier n reads bin d_bins[n] of the LDS spectrum; a thread owns fixed groups of 4 consecutive n, keeps
+// their bins and the previous symbol's values in registers and stores 4 + 4 soft bytes per group (any alignment).  A run
+// starts by transforming the symbol before it: 1/run of redundant work.
+#pragma clang fp contract(off)
+#include <cfloat>
+#include <cmath>
+
+#include "vit_internal.h"
+
+namespace {
+
+typedef uint32_t u32;
+typedef uint64_t u64;
+constexpr u32 RUN_MAX = 25;  // data symbols per workgroup at most: one extra transform per run is then <= 4 %
+
+struct TdArgs {
+    const float2* iq;
+    u64 nsamples, sym_stride, frame_stride, extent;  // extent: samples from a frame's start to its last read, + 1
+    const long long* start;
+    const float2* tw;
+    const float2* nco;
+    const uint2* rot;
+    u32 nco_shift;  // 32 - nco_bits
+    u32 lo, hi;     // the symbols (FFT) or data symbols (demod) [lo, hi) of every frame are produced
+    u32 run, runs;  // of them per workgroup, workgroups per frame
+    // spectra out
+    float2* out;
+    u64 out_sym_stride, out_frame_stride;
+    // demapping
+    const uint16_t* bins;
+    u32 K, fic_syms, cifs, per;
+    float gain;
+    uint8_t* fic;
+    uint8_t* ring;
+    u64 row_bytes, nrows, first_row, col;
+};
+
+
+// LDS index of point i.  Rows of 32 points are skewed by 4, rows of 256 by 1 more: the strided loads of the passes
+// (stride 2^s points between a thread's own, consecutive or 8 << s apart between lanes) and the bit-reversed stores of
+// the first pass (2^(m-5) apart between lanes) then spread over the 32 eight-byte bank pairs.
+constexpr u32 pad(u32 i) { return i + ((i >> 5) << 2) + (i >> 8); }
+// Point q of a thread's group in the pass behind s stages is base + (q << s), base = pass_base(T, s).  Its LDS index is
+// pad(base) + pad(q << s): the skew of a group's points does not depend on the thread, so one address register and
+// immediate offsets serve a pass (pad_is_affine checks it for every thread at compile time).
+constexpr u32 pass_base(u32 T, u32 s) { return ((T >> s) << (s + 3u)) + (T & ((1u << s) - 1u)); }
+constexpr bool pad_is_affine(u32 M) {
+    const u32 R1 = M % 3u ? M % 3u : 3u;
+    for (u32 s = R1; s < M; s += 3u)
+        for (u32 T = 0; T < (1u << M) / 8u; T++)
+            for (u32 q = 0; q < 8u; q++)
+                if (pad(pass_base(T, s) + (q << s)) != pad(pass_base(T, s)) + pad(q << s)) return false;
+    for (u32 i = 0; i < (1u << M); i++)  // the first pass stores aligned groups of at most 8 consecutive points
+        if (pad(i) != pad(i & ~7u) + (i & 7u)) return false;
+    return true;
+}
+
+template <u32 M>
+struct Cfg {
+    static constexpr u32 N = 1u << M;
+    static constexpr u32 TA = N / 8u;                  // threads that work on a symbol
+    static constexpr u32 TPB = TA < 64u ? 64u : TA;
+    static constexpr u32 R1 = M % 3u ? M % 3u : 3u;    // stages of the first pass
+    static constexpr u32 NP = (M - R1) / 3u;           // radix-8 passes behind it
+    // wavefronts per SIMD the registers are budgeted for: with rotation the prefetched phasors take 16 more (a workgroup
+    // of 1024 needs 4 in any case)
+    static constexpr u32 waves(bool rot) { return TPB == 1024u ? 4u : rot ? 3u : 4u; }
+    static constexpr u32 PADN = pad(N - 1u) + 1u;       // float2 of LDS for a symbol, then twpad(N/2 - 1) + 1 twiddles
+    static constexpr u32 LDS_BYTES = (PADN + N / 2u + N / 64u) * 8u;
+    static constexpr u32 CG = 2u;                      // groups of 4 carriers per thread: K <= N = 8 TA
+};
+
+__device__ __forceinline__ void bfly(float2& u, float2& v, float2 w) {
+    const float tr = w.x * v.x - w.y * v.y;
+    const float ti = w.x * v.y + w.y * v.x;
+    const float2 a = u;
+    u = make_float2(a.x + tr, a.y + ti);
+    v = make_float2(a.x - tr, a.y - ti);
+}
+__device__ __forceinline__ void bfly_one(float2& u, float2& v) {  // w = 1
+    const float2 a = u, t = v;
+    u = make_float2(a.x + t.x, a.y + t.y);
+    v = make_float2(a.x - t.x, a.y - t.y);
+}
+__device__ __forceinline__ void bfly_mj(float2& u, float2& v) {  // w = -j: t = (v.im, -v.re)
+    const float2 a = u, t = v;
+    u = make_float2(a.x + t.y, a.y - t.x);
+    v = make_float2(a.x - t.y, a.y + t.x);
+}
+
+// 3 stages on 8 points; w[h - 1 + jq]: the twiddle of stage h = 1, 2, 4 for the points q with q mod h = jq
+__device__ __forceinline__ void radix8(float2 (&v)[8], const float2 (&w)[7]) {
+#pragma unroll
+    for (u32 h = 1; h < 8; h *= 2)
+#pragma unroll
+        for (u32 q = 0; q < 8; q++)
+            if (!(q & h)) bfly(v[q], v[q + h], w[h - 1 + (q & (h - 1))]);
+}
+
+// stages 1 ... R1 on the 2^R1 points of one group of the first pass; e1, e3: the twiddles at 1/8 and 3/8 of a half turn
+template <u32 R1>
+__device__ __forceinline__ void first_stages(float2* v, float2 e1, float2 e3) {
+#pragma unroll
+    for (u32 q = 0; q < (1u << R1); q += 2) bfly_one(v[q], v[q + 1]);
+    if (R1 >= 2) {
+#pragma unroll
+        for (u32 q = 0; q < (1u << R1); q += 4) {
+            bfly_one(v[q], v[q + 2]);
+            bfly_mj(v[q + 1], v[q + 3]);
+        }
+    }
+    if (R1 >= 3) {
+        bfly_one(v[0], v[4]);
+        bfly(v[1], v[5], e1);
+        bfly_mj(v[2], v[6]);
+        bfly(v[3], v[7], e3);
+    }
+}
+
+constexpr u32 bitrev(u32 x, u32 bits) {
+    u32 r = 0;
+    for (u32 b = 0; b < bits; b++) r |= (x >> b & 1u) << (bits - 1u - b);
+    return r;
+}
+
+// the two soft bytes of one carrier (low byte: bit n, next byte: bit n + K) from a = z[l], b = z[l-1]: vit_ofdm.hip's
+__device__ __forceinline__ u32 soft_pair(float ar, float ai, float br, float bi, float gain) {
+    const float re = ar * br + ai * bi;
+    const float im = ai * br - ar * bi;
+    const float nrm = __builtin_fabsf(re) + __builtin_fabsf(im);
+    u32 q = 0x8080u;
+    if (nrm >= 0x1p-64f && nrm <= FLT_MAX) {  // false for NaN
+        const float s = gain / nrm;
+        const float q0 = __builtin_fminf(__builtin_fmaxf(128.0f - __builtin_rintf(re * s), 0.0f), 255.0f);
+        const float q1 = __builtin_fminf(__builtin_fmaxf(128.0f - __builtin_rintf(im * s), 0.0f), 255.0f);
+        q = (u32)q0 | (u32)q1 << 8;
+    }
+    return q;
+}
+
+// LDS index of twiddle k: the lanes of a pass read twiddles a power of two apart
+constexpr u32 twpad(u32 k) { return k + (k >> 5); }
+
+// the 7 twiddles of thread T's group in the pass behind s stages, in radix8's order, from the LDS copy of the table
+template <u32 M>
+__device__ __forceinline__ void load_twiddles(const float2* tw, u32 T, u32 s, float2 (&w)[7]) {
+    const u32 j0 = T & ((1u << s) - 1u);
+#pragma unroll
+    for (u32 a = 0; a < 3; a++)
+#pragma unroll
+        for (u32 jq = 0; jq < (1u << a); jq++) w[(1u << a) - 1u + jq] = tw[twpad((j0 + (jq << s)) * ((1u << M) >> (s + a + 1u)))];
+}
+
+template <u32 M, bool ROT>
+struct Samples {
+    float2 x[8];
+    float2 w[ROT ? 8 : 1];
+};
+
+// symbol l's samples of thread T: group k of the first pass is T + k*TA, its point c is sample gid + c*N/R
+template <u32 M, bool ROT>
+__device__ __forceinline__ void load_samples(const TdArgs& A, const float2* frame, u32 l, u32 ph0, u32 step, u32 T,
+                                             Samples<M, ROT>& s) {
+    typedef Cfg<M> C;
+    constexpr u32 R = 1u << C::R1, NG = C::N / R;
+    const float2* sym = frame + (u64)l * A.sym_stride;
+    const u32 n0 = (u32)((u64)l * A.sym_stride);  // mod 2^32, like the phase
+#pragma unroll
+    for (u32 k = 0; k < 8u / R; k++)
+#pragma unroll
+        for (u32 c = 0; c < R; c++) {
+            const u32 i = T + k * C::TA + c * NG;
+            s.x[k * R + c] = sym[i];
+            if (ROT) s.w[k * R + c] = A.nco[(ph0 + (n0 + i) * step) >> A.nco_shift];
+        }
+}
+
+template <u32 M, bool ROT, bool DEMAP>
+__global__ __launch_bounds__(Cfg<M>::TPB) __attribute__((amdgpu_waves_per_eu(Cfg<M>::waves(ROT), Cfg<M>::waves(ROT)))) void vit_ofdm_td_kernel(TdArgs A) {
+    typedef Cfg<M> C;
+    constexpr u32 N = C::N, TA = C::TA, R1 = C::R1, R = 1u << R1, NP = C::NP;
+    extern __shared__ float2 lds_td[];
+    const u32 T = threadIdx.x;
+    const bool active = C::TPB == TA || T < TA;
+    const u64 t = blockIdx.x / A.runs;
+    long long st = (long long)(t * A.frame_stride);
+    if (A.start) {  // the frame is skipped unless all its reads are inside [0, nsamples)
+        st = A.start[t];
+        if (st < 0 || (u64)st > A.nsamples || A.extent > A.nsamples - (u64)st) return;
+    }
+    const float2* frame = A.iq + st;
+    const u32 s0 = A.lo + (u32)(blockIdx.x % A.runs) * A.run, s1 = s0 + A.run < A.hi ? s0 + A.run : A.hi;
+    const u32 l1 = DEMAP ? s1 : s1 - 1u;  // the symbols s0 ... l1 are transformed
+    u32 ph0 = 0, step = 0;
+    if (ROT) {
+        const uint2 r = A.rot[t];
+        ph0 = r.x;
+        step = r.y;
+    }
+
+    // the twiddles live in LDS behind the symbol (a thread's 7 per pass are the same for every symbol, but 21 or 28
+    // float2 of registers cost more occupancy than their loads cost LDS cycles)
+    static_assert(pad_is_affine(M), "pad() must skew every thread's group alike");
+    float2* tw_lds = lds_td + Cfg<M>::PADN;
+    for (u32 i = T; i < N / 2u; i += C::TPB) tw_lds[twpad(i)] = A.tw[i];
+    float2 e1 = make_float2(1.f, 0.f), e3 = e1;
+    if (R1 == 3) {
+        e1 = A.tw[N / 8u];
+        e3 = A.tw[3u * N / 8u];
+    }
+    __syncthreads();
+    // the thread's carriers: groups T + j*TPB of 4 consecutive n
+    u32 bin[C::CG][4];
+    float2 prev[C::CG][4];
+    if (DEMAP) {
+#pragma unroll
+        for (u32 j = 0; j < C::CG; j++)
+#pragma unroll
+            for (u32 c = 0; c < 4; c++) {
+                const u32 n = 4u * (T + j * C::TPB) + c;
+                bin[j][c] = n < A.K ? (u32)A.bins[n] : N;  // >= N: no carrier, erasures
+                prev[j][c] = make_float2(0.f, 0.f);
+            }
+    }
+
+    Samples<M, ROT> smp;
+    if (active) load_samples<M, ROT>(A, frame, s0, ph0, step, T, smp);
+    for (u32 l = s0; l <= l1; l++) {
+        if (active) {
+#pragma unroll
+            for (u32 k = 0; k < 8u / R; k++) {
+                float2 v[R];
+#pragma unroll
+                for (u32 c = 0; c < R; c++) {
+                    float2 x = smp.x[k * R + c];
+                    if (ROT) {
+                        const float2 ww = smp.w[k * R + c];
+                        x = make_float2(x.x * ww.x - x.y * ww.y, x.x * ww.y + x.y * ww.x);
+                    }
+                    v[bitrev(c, R1)] = x;
+                }
+                first_stages<R1>(v, e1, e3);
+                float2* g = lds_td + pad(R * (__builtin_bitreverse32(T + k * TA) >> (32u - (M - R1))));
+#pragma unroll
+                for (u32 q = 0; q < R; q++) g[q] = v[q];
+            }
+            if (l < l1) load_samples<M, ROT>(A, frame, l + 1u, ph0, step, T, smp);
+        }
+        __syncthreads();
+#pragma unroll
+        for (u32 p = 0; p < NP; p++) {
+            if (active) {
+                const u32 s = R1 + 3u * p;
+                float2* g = lds_td + pad(pass_base(T, s));
+                float2 v[8];
+#pragma unroll
+                for (u32 q = 0; q < 8; q++) v[q] = g[pad(q << s)];
+                float2 w[7];
+                load_twiddles<M>(tw_lds, T, s, w);
+                radix8(v, w);
+#pragma unroll
+                for (u32 q = 0; q < 8; q++) g[pad(q << s)] = v[q];
+            }
+            __syncthreads();
+        }
+        if (DEMAP) {
+            const u32 s = l - 1u;  // the data symbol this transform completes (none at l = s0)
+            uint8_t* dst = nullptr;
+            if (l > s0) {
+                if (s < A.fic_syms) {
+                    dst = A.fic + (t * A.fic_syms + s) * 2u * A.K;
+                } else {
+                    const u32 m = s - A.fic_syms, c = m / A.per;
+                    u64 row = A.first_row + t * A.cifs + c;
+                    if (row >= A.nrows) row -= A.nrows;
+                    dst = A.ring + row * A.row_bytes + A.col + (u64)(m - c * A.per) * 2u * A.K;
+                }
+            }
+#pragma unroll
+            for (u32 j = 0; j < C::CG; j++) {
+                const u32 n0 = 4u * (T + j * C::TPB);
+                if (n0 >= A.K) continue;
+                u32 lo4 = 0, hi4 = 0;
+#pragma unroll
+                for (u32 c = 0; c < 4; c++) {
+                    const bool named = bin[j][c] < N;
+                    const float2 a = named ? lds_td[pad(bin[j][c])] : make_float2(0.f, 0.f);
+                    const u32 q = named && dst ? soft_pair(a.x, a.y, prev[j][c].x, prev[j][c].y, A.gain) : 0x8080u;
+                    lo4 |= (q & 0xFFu) << (8u * c);
+                    hi4 |= (q >> 8) << (8u * c);
+                    prev[j][c] = a;
+                }
+                if (!dst) continue;
+                if (n0 + 4u <= A.K) {
+                    __builtin_memcpy(dst + n0, &lo4, 4);  // unaligned global_store_dword
+                    __builtin_memcpy(dst + A.K + n0, &hi4, 4);
+                } else {
+                    for (u32 c = 0; n0 + c < A.K; c++) {
+                        dst[n0 + c] = (uint8_t)(lo4 >> (8u * c));
+                        dst[A.K + n0 + c] = (uint8_t)(hi4 >> (8u * c));
+                    }
+                }
+            }
+        } else {
+            float2* o = A.out + t * A.out_frame_stride + (u64)l * A.out_sym_stride;
+            for (u32 i = T; i < N; i += C::TPB) o[i] = lds_td[pad(i)];
+        }
+        __syncthreads();  // the spectrum has been read: the next symbol's first pass may overwrite it
+    }
+}
+
+template <u32 M, bool ROT, bool DEMAP>
+hipError_t launch3(const TdArgs& A, u64 grid, hipStream_t stream) {
+    const size_t lds = Cfg<M>::LDS_BYTES;
+    if (lds > 64u * 1024u) {
+        static uint64_t optin_done = 0;
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+        const void* ks[1] = {reinterpret_cast<const void*>(&vit_ofdm_td_kernel<M, ROT, DEMAP>)};
+        const hipError_t e = vit_optin_dynamic_lds(ks, 1, 160 * 1024, dev, &optin_done);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((vit_ofdm_td_kernel<M, ROT, DEMAP>), dim3((unsigned)grid), dim3(Cfg<M>::TPB), lds, stream, A);
+    return hipGetLastError();
+}
+
+template <u32 M>
+hipError_t launch2(const TdArgs& A, bool demap, u64 grid, hipStream_t stream) {
+    if (A.rot) return demap ? launch3<M, true, true>(A, grid, stream) : launch3<M, true, false>(A, grid, stream);
+    return demap ? launch3<M, false, true>(A, grid, stream) : launch3<M, false, false>(A, grid, stream);
+}
+
+// workgroups of the TdArgs' symbol range: about 8 per CU over the whole grid, RUN_MAX symbols per run at most
+hipError_t launch(TdArgs& A, u32 nfft, bool demap, int64_t nframes, hipStream_t stream) {
+    if (nframes <= 0 || A.hi <= A.lo) return hipSuccess;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    const u64 target = 8ull * (u64)vit_device_cus(dev);
+    const u32 nsym = A.hi - A.lo;
+    u64 rpf = (target + (u64)nframes - 1) / (u64)nframes;
+    if (rpf > nsym) rpf = nsym;
+    u32 run = (u32)((nsym + rpf - 1) / rpf);
+    if (run > RUN_MAX) run = RUN_MAX;
+    A.run = run;
+    A.runs = (nsym + run - 1) / run;
+    const u64 grid = (u64)nframes * A.runs;
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    switch (nfft) {
+        case 64: return launch2<6>(A, demap, grid, stream);
+        case 128: return launch2<7>(A, demap, grid, stream);
+        case 256: return launch2<8>(A, demap, grid, stream);
+        case 512: return launch2<9>(A, demap, grid, stream);
+        case 1024: return launch2<10>(A, demap, grid, stream);
+        case 2048: return launch2<11>(A, demap, grid, stream);
+        case 4096: return launch2<12>(A, demap, grid, stream);
+        case 8192: return launch2<13>(A, demap, grid, stream);
+    }
+    return hipErrorInvalidValue;
+}
+
+TdArgs input_args(const vit_iq_input& in, u32 nfft, u32 nsyms) {
+    TdArgs A = {};
+    A.iq = reinterpret_cast<const float2*>(in.d_iq);
+    A.nsamples = in.nsamples;
+    A.sym_stride = in.sym_stride;
+    A.frame_stride = in.frame_stride;
+    A.extent = (u64)(nsyms - 1u) * in.sym_stride + nfft;  // the caller has checked that it does not overflow
+    A.start = reinterpret_cast<const long long*>(in.d_start);
+    A.tw = reinterpret_cast<const float2*>(in.d_tw);
+    if (in.d_rot) {
+        A.nco = reinterpret_cast<const float2*>(in.d_nco);
+        A.rot = reinterpret_cast<const uint2*>(in.d_rot);
+        A.nco_shift = 32u - in.nco_bits;
+    }
+    return A;
+}
+
+// exact at multiples of an eighth of a turn, binary64 cos / sin rounded to binary32 elsewhere: (cos, sgn * sin)(2 pi k / n)
+void unit_pair(u64 k, u64 n, double sgn, float* out) {
+    static const double PI = 3.14159265358979323846;
+    if ((8u * k) % n == 0) {
+        const float r = (float)std::sqrt(0.5);
+        const float c[8] = {1.f, r, 0.f, -r, -1.f, -r, 0.f, r}, s[8] = {0.f, r, 1.f, r, 0.f, -r, -1.f, -r};
+        const u32 e = (u32)(8u * k / n) & 7u;
+        out[0] = c[e];
+        out[1] = s[e] == 0.f ? 0.f : (float)(sgn * (double)s[e]);
+        return;
+    }
+    const double a = 2.0 * PI * (double)k / (double)n;
+    out[0] = (float)std::cos(a);
+    out[1] = (float)(sgn * std::sin(a));
+}
+
+}  // namespace
+
+int64_t vit_fft_twiddles_host(uint32_t nfft, float* h_tw) {
+    if (!h_tw || nfft < 64u || nfft > 8192u || (nfft & (nfft - 1u)) != 0) return -1;
+    for (u32 k = 0; k < nfft / 2u; k++) unit_pair(k, nfft, -1.0, h_tw + 2u * k);
+    return nfft / 2u;
+}
+
+int64_t vit_nco_table_host(uint32_t nco_bits, float* h_nco) {
+    if (!h_nco || nco_bits < 1u || nco_bits > 20u) return -1;
+    const u64 n = 1ull << nco_bits;
+    for (u64 k = 0; k < n; k++) unit_pair(k, n, 1.0, h_nco + 2u * k);
+    return (int64_t)n;
+}
+
+hipError_t vit_launch_ofdm_fft(const vit_iq_input& in, uint32_t nfft, uint32_t nsyms, int64_t nframes, float* d_fft,
+                               uint64_t out_sym_stride, uint64_t out_frame_stride, hipStream_t stream) {
+    TdArgs A = input_args(in, nfft, nsyms);
+    A.lo = 0;
+    A.hi = nsyms;
+    A.out = reinterpret_cast<float2*>(d_fft);
+    A.out_sym_stride = out_sym_stride;
+    A.out_frame_stride = out_frame_stride;
+    return launch(A, nfft, false, nframes, stream);
+}
+
+hipError_t vit_launch_ofdm_demod(const vit_iq_input& in, const uint16_t* d_bins, const vit_ofdm_shape& shape, float gain,
+                                 int64_t nframes, uint8_t* d_fic, const vit_cif_ring* ring, uint64_t col, hipStream_t stream) {
+    TdArgs A = input_args(in, shape.nfft, shape.nsyms);
+    A.bins = d_bins;
+    A.K = shape.ncarriers;
+    A.fic_syms = shape.fic_syms;
+    A.cifs = shape.cifs;
+    A.per = (shape.nsyms - 1u - shape.fic_syms) / shape.cifs;
+    A.lo = d_fic ? 0u : shape.fic_syms;
+    A.hi = ring ? shape.nsyms - 1u : shape.fic_syms;
+    A.gain = gain;
+    A.fic = d_fic;
+    if (ring) {
+        A.ring = const_cast<uint8_t*>(ring->d_base);  // this call is the ring's writer
+        A.row_bytes = ring->row_bytes;
+        A.nrows = ring->nrows;
+        A.first_row = ring->first_row;
+        A.col = col;
+    }
+    return launch(A, shape.nfft, true, nframes, stream);
+}
