@@ -388,7 +388,8 @@ int vit_ofdm_demap_dev(const float *d_fft, uint64_t sym_stride, uint64_t frame_s
  * phase reference symbol (the caller places it inside the guard interval as its time synchronisation says); the useful
  * part of symbol l of frame t is samples start_t + l*sym_stride ... + nfft - 1.  Nothing else is read: not the samples
  * between useful parts, not the null symbol.  Any sample position is allowed; only d_iq must be 8-byte aligned.
- * Out of scope: time and frequency estimation, integer sample formats, resampling, channel-state weighting. */
+ * The two tables come from vit_ofdm_sync_dev ("From the coarse start", below) or from the caller's own estimator.
+ * Out of scope: first acquisition (finding the null symbol), integer sample formats, resampling, channel-state weighting. */
 typedef struct vit_iq_input {
     const float    *d_iq;         /* interleaved (re, im) float32 samples, 8-byte aligned */
     uint64_t        nsamples;     /* complex samples in d_iq: nothing at or beyond it is read */
@@ -434,7 +435,7 @@ int64_t vit_nco_table(uint32_t nco_bits, float *h_nco);
 /* vit_ofdm_fft_dev: steps 1 and 2 for symbols 0 ... nsyms-1 of nframes frames; X of symbol l of frame t goes to complex
  * elements t*out_frame_stride + l*out_sym_stride ... + nfft - 1 of d_fft, the layout vit_ofdm_demap_dev reads (d_fft
  * 16-byte aligned, both output strides even, out_sym_stride >= nfft); nothing else of d_fft is written.  For callers
- * that need a spectrum (the phase reference symbol for synchronisation, a channel estimate).
+ * that need a spectrum (a channel estimate, an estimator of their own; vit_ofdm_sync_dev needs none).
  * vit_ofdm_demod_dev: steps 1 to 3; d_bins, shape, gain, d_fic, ring and col as in vit_ofdm_demap_dev, with the same
  * destinations, rules and guarantees (no write outside the named bytes, other ring rows untouched, no bin that d_bins
  * does not name influences any output).
@@ -450,6 +451,78 @@ int vit_ofdm_fft_dev(const vit_iq_input *in, uint32_t nfft, uint32_t nsyms, int6
                      uint64_t out_sym_stride, uint64_t out_frame_stride, void *stream);
 int vit_ofdm_demod_dev(const vit_iq_input *in, const uint16_t *d_bins, const vit_ofdm_shape *shape, float gain,
                        int64_t nframes, uint8_t *d_fic, const vit_cif_ring *ring, uint64_t col, void *stream);
+
+/* From the coarse start: fine time and frequency.  One call reads the samples and writes exactly the two per-frame DEVICE
+ * tables vit_ofdm_demod_dev reads - d_start[t] and d_rot[t] = {phase0, step} - so nothing leaves the device between the
+ * samples and the soft bytes.  It is the per-frame TRACKING step: it starts from a coarse start c that is right to within
+ * +-W samples (the previous frame's start plus frame_stride, or the caller's null-symbol search) and a carrier offset of
+ * less than M + 1/2 carrier spacings.  First acquisition (finding the null symbol in an unaligned stream) stays the
+ * caller's.  The transmitted phase reference symbol is a caller-supplied DEVICE table d_prs: nfft complex binary32 values
+ * in FFT order, zero on unused bins (the library still holds no table of the standard except the bin table).
+ * Like the rest of the front end the result is defined bit for bit. */
+typedef struct vit_sync_params {
+    uint32_t nfft;        /* power of two 64 ... 8192 */
+    uint32_t nsyms;       /* symbols per frame incl. the phase reference (read span, skip rule); >= 2 */
+    uint32_t cp_symbols;  /* guards used for the fractional estimate: those in front of symbols 1 ... cp_symbols; 1 ... nsyms-1 */
+    uint32_t W;           /* timing uncertainty, samples; 2*W < guard and 2*W < nfft, guard = in->sym_stride - nfft < 2^31 */
+    uint32_t M;           /* integer carrier offsets searched: -M ... M; 0 ... 64, 2*M < nfft */
+    float    thr;         /* first-path threshold, (0, 1]; 1 = the strongest path */
+    int32_t  backoff;     /* samples subtracted from the found start (places it inside the guard) */
+    int64_t  first_start; /* coarse start of frame t = first_start + t*frame_stride when in->d_start is NULL */
+} vit_sync_params;
+/* Definition.  Every operation is one IEEE binary32 operation, rounded to nearest-even, in exactly this order, never
+ * contracted into an FMA.  x: the samples; S = sym_stride, G = S - nfft, c = the frame's coarse start (in->d_start[t] or
+ * first_start + t*frame_stride); P = d_prs; tw, nco: the tables of vit_iq_input.  Products of complex values:
+ *   a * conj(b) = ( fl(fl(a.re*b.re) + fl(a.im*b.im)),  fl(fl(a.im*b.re) - fl(a.re*b.im)) )
+ * Long sums.  NACC = max(64, nfft/8) accumulators start at +0; element e of a sum (e = 0, 1, ... in the order given) is
+ * added to accumulator e mod NACC, in ascending e: acc = fl(acc + element), component by component.  Then the
+ * accumulators meet in the tree of adjacent pairs: v[i] = fl(v[2i] + v[2i+1]) until one value is left.  The grouping
+ * depends on nfft alone - never on nframes, the launch or the device.
+ * A. Fractional offset.  Elements (l, k), l = 1 ... cp_symbols, k = 0 ... G-2W-1, l-major: e = (l-1)*(G-2W) + k, with
+ *    n = c + l*S - G + W + k (inside the guard of symbol l wherever the true start lies in c +- W), a = x[n], b = x[n+nfft]:
+ *      gamma += conj(a) * b = ( fl(fl(a.re*b.re) + fl(a.im*b.im)),  fl(fl(a.re*b.im) - fl(a.im*b.re)) )
+ *      E     += fl( fl(fl(a.re*a.re) + fl(a.im*a.im)) + fl(fl(b.re*b.re) + fl(b.im*b.im)) )
+ *    turn = atan2(gamma.im, gamma.re) / 2 pi in [-1/2, 1/2] by this graph: ax = |gamma.re|, ay = |gamma.im|,
+ *    mx = max(ax, ay), mn = min(ax, ay); mx = 0 gives turn = 0; else q = fl(mn / mx), s = fl(q*q),
+ *      p = C6;  p = fl(fl(p*s) + Ci) for i = 5 ... 0;  r = fl(p*q)                  (r = atan(q) / 2 pi, 0 ... 1/8)
+ *      if ay > ax: r = fl(0.25 - r);   if gamma.re < 0: r = fl(0.5 - r);   if gamma.im < 0: r = -r;   turn = r
+ *    with the coefficients below (error of the graph against atan2: under 2^-23 turn).
+ *      step_frac = (-rint(fl(turn * 2^32/nfft))) mod 2^32                      rint: ties to even; the product is exact
+ * B. Phase reference spectrum.  The window starts at w0 = c - W.  Sample i < nfft, x[w0 + i], is rotated as in step 1 of
+ *    "From the samples" with phase0 = 0, step = step_frac, n = i; Y = the FFT of step 2 of it.
+ * C. Integer offset.  D[k] = Y[k] * conj(Y[k-1]), R[k] = P[k] * conj(P[k-1]), indices mod nfft.  For m = -M ... M:
+ *      C[m] = sum over k = 0 ... nfft-1 (a long sum, e = k) of D[(k+m) mod nfft] * conj(R[k])
+ *      metric[m] = fl(fl(C.re*C.re) + fl(C.im*C.im))
+ *    m^ = the first maximum in the order -M ... M (a later m replaces it only if its metric is greater).
+ * D. Timing.  Z[k] = Y[(k+m^) mod nfft] * conj(P[k]);  h = conj(FFT(conj Z)), the same FFT graph, no scaling;
+ *      p[n] = fl(fl(h.re*h.re) + fl(h.im*h.im));   psum = the long sum of p[n], e = n = 0 ... nfft-1
+ *      pmax = max of p[0 ... 2W];   tau = the first n <= 2W with p[n] >= fl(thr * pmax)
+ * E. Outputs.  d_start_out[t] = c - W + tau - backoff;   d_rot_out[t] = {0, (step_frac - m^ * (2^32/nfft)) mod 2^32};
+ *    d_info[8t ...] = {int32 m^, int32 tau, gamma.re, gamma.im, E, metric[m^], pmax, psum}  (optional: quality figures -
+ *    |gamma| / (E/2) is the guard correlation, pmax / psum the share of the first paths' power).
+ * Domain: the samples' domain of "From the samples", and no operation above overflows - with |P[k]| <= 1 that holds for
+ * sample magnitudes up to 2^12 at every nfft.  Underflow is gradual: denormal results are kept, as IEEE arithmetic has
+ * them.  All-zero samples are inside the domain: every comparison ties, m^ = -M, tau = 0, turn = 0.  Outside it the
+ * frame's outputs are unspecified; nothing but the call's output words is written.
+ * Skip rule: a frame's reads are taken to span c - W ... c + (nsyms-1)*S + nfft - 1 + W.  With in->d_start given, a frame
+ * whose span is not inside [0, nsamples) is skipped on the device: it gets start -1, rot {0, 0} and info zeros, so
+ * vit_ofdm_demod_dev skips it too by its own rule.  Without in->d_start such a frame is VIT_ERR_ARG.
+ * in: the struct vit_ofdm_demod_dev takes.  in->d_start, if given, is the coarse table (d_start_out may be the same
+ * pointer); in->d_nco and in->nco_bits are required; in->d_rot must be NULL.  d_info may be NULL.
+ * Argument rules as the other *_dev calls: VIT_ERR_NO_DEVICE first; VIT_ERR_ARG (with vit_last_error()) for a NULL in, p,
+ * d_iq, d_tw, d_nco, d_prs, d_start_out or d_rot_out; a d_iq, d_tw, d_nco, d_start, d_prs, d_start_out or d_rot_out that is
+ * not 8-byte aligned or a d_info that is not 4-byte aligned; nco_bits outside 1 ... 20; in->d_rot set; every range in the
+ * struct's comments (2*W >= guard among them); a span beyond 2^64 samples; nframes < 0.  An empty batch returns VIT_OK and
+ * writes nothing; everything is enqueued on `stream` without synchronising. */
+#define VIT_SYNC_ATAN_C0  0x1.45f2b4p-3f
+#define VIT_SYNC_ATAN_C1 -0x1.b26414p-5f
+#define VIT_SYNC_ATAN_C2  0x1.0240f6p-5f
+#define VIT_SYNC_ATAN_C3 -0x1.591268p-6f
+#define VIT_SYNC_ATAN_C4  0x1.9f40a4p-7f
+#define VIT_SYNC_ATAN_C5 -0x1.5e8136p-8f
+#define VIT_SYNC_ATAN_C6  0x1.1c32c4p-10f
+int vit_ofdm_sync_dev(const vit_iq_input *in, const vit_sync_params *p, const float *d_prs, int64_t nframes,
+                      int64_t *d_start_out, uint32_t *d_rot_out, uint32_t *d_info, void *stream);
 
 /* Kernel selection (the analogue of the reference's dispatcher, setupdll.cpp:195-270):
  *   0 = auto: launches of up to 2048 frames (they cannot fill the chip) take the latency kernel - one

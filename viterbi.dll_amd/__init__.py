@@ -30,7 +30,7 @@ EXPORTS = [
     "vit_decode_fic_dev", "vit_dabplus_punctured_superframes_dev",
     "vit_time_deinterleave_dev", "vit_decode_punctured_ti_dev", "vit_dabplus_ti_superframes_dev",
     "vit_freq_interleave_bins", "vit_ofdm_demap_dev",
-    "vit_fft_twiddles", "vit_nco_table", "vit_ofdm_fft_dev", "vit_ofdm_demod_dev",
+    "vit_fft_twiddles", "vit_nco_table", "vit_ofdm_fft_dev", "vit_ofdm_demod_dev", "vit_ofdm_sync_dev",
     "vit_decode_stream_multi",
 ]
 MULTI_LOOPBACK = 0x1
@@ -77,6 +77,12 @@ class IqInput(C.Structure):
     _fields_ = [("d_iq", C.c_void_p), ("nsamples", C.c_uint64), ("sym_stride", C.c_uint64), ("frame_stride", C.c_uint64),
                 ("d_start", C.c_void_p), ("d_tw", C.c_void_p), ("d_nco", C.c_void_p), ("nco_bits", C.c_uint32),
                 ("d_rot", C.c_void_p)]
+
+
+class SyncParams(C.Structure):
+    """vit_sync_params of include/viterbi_amd.h: SyncParams(nfft, nsyms, cp_symbols, W, M, thr, backoff, first_start)"""
+    _fields_ = [("nfft", C.c_uint32), ("nsyms", C.c_uint32), ("cp_symbols", C.c_uint32), ("W", C.c_uint32), ("M", C.c_uint32),
+                ("thr", C.c_float), ("backoff", C.c_int32), ("first_start", C.c_int64)]
 
 
 # the four transmission modes of EN 300 401 as shapes (examples: the library compiles in no table of modes)
@@ -156,6 +162,7 @@ def lib():
         L.vit_nco_table.restype = C.c_int64
         L.vit_ofdm_fft_dev.argtypes = [pi, C.c_uint32, C.c_uint32, C.c_int64, vp, C.c_uint64, C.c_uint64, vp]
         L.vit_ofdm_demod_dev.argtypes = [pi, vp, C.POINTER(OfdmShape), C.c_float, C.c_int64, vp, pr, C.c_uint64, vp]
+        L.vit_ofdm_sync_dev.argtypes = [pi, C.POINTER(SyncParams), vp, C.c_int64, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -586,6 +593,36 @@ def ofdm_demod_dev(d_iq, shape, d_bins, gain, nframes, d_tw, sym_stride, frame_s
     ring = None if d_ring is None else C.byref(cif_ring(d_ring, first_row))
     _check(lib().vit_ofdm_demod_dev(C.byref(inp), _ptr(d_bins), C.byref(shape), float(gain), nframes, _ptr(d_fic), ring, col,
                                     _stream_ptr(stream)), "vit_ofdm_demod_dev")
+
+
+def ofdm_sync_dev(d_iq, nfft, nsyms, nframes, d_tw, sym_stride, d_nco, nco_bits, d_prs, d_start_out, d_rot_out, W, M,
+                  cp_symbols=None, thr=0.5, backoff=0, frame_stride=None, first_start=0, d_start=None, d_info=None,
+                  stream=None, nsamples=None):
+    """From the coarse start (include/viterbi_amd.h): per frame the fine start and the carrier offset, written as the
+    tables ofdm_demod_dev reads - d_start_out (int64 CUDA tensor, nframes) and d_rot_out (CUDA tensor of 4-byte elements,
+    {0, step} per frame).  Input arguments as iq_input; the coarse starts are d_start (d_start_out may be the same
+    tensor) or first_start + t*frame_stride.  d_prs: the transmitted phase reference symbol, nfft values in FFT order
+    (complex64 or float32 CUDA tensor); cp_symbols defaults to nsyms - 1; d_info (optional): CUDA tensor of 4-byte
+    elements, 8 words per frame."""
+    if d_nco is None:
+        raise ValueError("d_nco is required")
+    if frame_stride is None and d_start is None:
+        raise ValueError("frame_stride or d_start is required")
+    if not d_prs.is_cuda or str(d_prs.dtype) not in ("torch.complex64", "torch.float32"):
+        raise ValueError("d_prs must be a complex64 or float32 CUDA tensor")
+    if d_prs.numel() * d_prs.element_size() < 8 * int(nfft):
+        raise ValueError("d_prs must hold nfft complex values")
+    if not d_start_out.is_cuda or str(d_start_out.dtype) != "torch.int64" or d_start_out.numel() < nframes:
+        raise ValueError("d_start_out must be an int64 CUDA tensor of nframes elements")
+    if not d_rot_out.is_cuda or d_rot_out.element_size() != 4 or d_rot_out.numel() < 2 * nframes:
+        raise ValueError("d_rot_out must be a CUDA tensor of 2*nframes 4-byte elements (uint32 pairs)")
+    if d_info is not None and (not d_info.is_cuda or d_info.element_size() != 4 or d_info.numel() < 8 * nframes):
+        raise ValueError("d_info must be a CUDA tensor of 8*nframes 4-byte elements")
+    inp = iq_input(d_iq, d_tw, sym_stride, frame_stride, d_start, d_nco, nco_bits, None, nsamples)
+    par = SyncParams(int(nfft), int(nsyms), int(nsyms) - 1 if cp_symbols is None else int(cp_symbols), int(W), int(M),
+                     float(thr), int(backoff), int(first_start))
+    _check(lib().vit_ofdm_sync_dev(C.byref(inp), C.byref(par), _ptr(d_prs), nframes, _ptr(d_start_out), _ptr(d_rot_out),
+                                   _ptr(d_info), _stream_ptr(stream)), "vit_ofdm_sync_dev")
 
 
 def decode_stream_multi(d_symbols_u8, d_out, framebits, nframes, devices, chunk_frames, root_frames=-1, flags=0,

@@ -1395,6 +1395,63 @@ int vit_ofdm_demod_dev(const vit_iq_input* in, const uint16_t* d_bins, const vit
     return VIT_OK;
 }
 
+// ---- from the coarse start: fine time and frequency (vit_ofdm_sync.hip) ----------------------------------------------------
+int vit_ofdm_sync_dev(const vit_iq_input* in, const vit_sync_params* p, const float* d_prs, int64_t nframes,
+                      int64_t* d_start_out, uint32_t* d_rot_out, uint32_t* d_info, void* stream) {
+    const char* who = "vit_ofdm_sync_dev";
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (!in || !p || !d_prs || !d_start_out || !d_rot_out || !in->d_iq || !in->d_tw || !in->d_nco || nframes < 0) {
+        set_err("%s: bad arguments (NULL in, p, d_iq, d_tw, d_nco, d_prs, d_start_out or d_rot_out, or nframes=%lld < 0)", who,
+                (long long)nframes);
+        return VIT_ERR_ARG;
+    }
+    if (((uintptr_t)in->d_iq & 7u) != 0 || ((uintptr_t)in->d_tw & 7u) != 0 || ((uintptr_t)in->d_nco & 7u) != 0 ||
+        ((uintptr_t)in->d_start & 7u) != 0 || ((uintptr_t)d_prs & 7u) != 0 || ((uintptr_t)d_start_out & 7u) != 0 ||
+        ((uintptr_t)d_rot_out & 7u) != 0 || ((uintptr_t)d_info & 3u) != 0) {
+        set_err("%s: bad arguments (d_iq, d_tw, d_nco, d_start, d_prs, d_start_out and d_rot_out must be 8-byte aligned, d_info "
+                "4-byte aligned)", who);
+        return VIT_ERR_ARG;
+    }
+    if (in->d_rot || in->nco_bits < 1u || in->nco_bits > 20u) {
+        set_err("%s: bad arguments (d_rot must be NULL - the call writes that table -, nco_bits 1 ... 20, got %u)", who,
+                in->nco_bits);
+        return VIT_ERR_ARG;
+    }
+    if (p->nfft < 64u || p->nfft > 8192u || (p->nfft & (p->nfft - 1u)) != 0 || p->nsyms < 2u || p->cp_symbols < 1u ||
+        p->cp_symbols > p->nsyms - 1u || p->M > 64u || 2u * p->M >= p->nfft || !(p->thr > 0.0f && p->thr <= 1.0f)) {
+        set_err("%s: bad arguments (nfft=%u, a power of two 64 ... 8192; nsyms=%u >= 2; cp_symbols=%u, 1 ... nsyms-1; M=%u, 0 ... "
+                "64 and 2*M < nfft; thr=%g, 0 < thr <= 1)", who, p->nfft, p->nsyms, p->cp_symbols, p->M, (double)p->thr);
+        return VIT_ERR_ARG;
+    }
+    const uint64_t guard = in->sym_stride >= p->nfft ? in->sym_stride - p->nfft : 0;
+    if (guard == 0 || guard > 0x7FFFFFFFull || 2ull * p->W >= guard || 2ull * p->W >= p->nfft) {
+        set_err("%s: bad arguments (W=%u: 2*W < guard and 2*W < nfft, guard = sym_stride %llu - nfft %u, 0 < guard < 2^31)", who,
+                p->W, (unsigned long long)in->sym_stride, p->nfft);
+        return VIT_ERR_ARG;
+    }
+    // a frame's reads: c - W ... c + (nsyms-1)*sym_stride + nfft - 1 + W
+    const unsigned __int128 span = (unsigned __int128)(p->nsyms - 1u) * in->sym_stride + p->nfft + 2ull * p->W;
+    if (span > (unsigned __int128)UINT64_MAX) {
+        set_err("%s: bad arguments (a frame of %u symbols at sym_stride %llu spans beyond 2^64 samples)", who, p->nsyms,
+                (unsigned long long)in->sym_stride);
+        return VIT_ERR_ARG;
+    }
+    if (!in->d_start && nframes > 0) {
+        const __int128 first = (__int128)p->first_start - (__int128)p->W;
+        const __int128 end = first + (__int128)((unsigned __int128)(uint64_t)(nframes - 1) * in->frame_stride) + (__int128)span;
+        if (first < 0 || end > (__int128)in->nsamples || (unsigned __int128)(uint64_t)(nframes - 1) * in->frame_stride > (unsigned __int128)INT64_MAX) {
+            set_err("%s: bad arguments (%lld frames from first_start %lld at frame_stride %llu read outside [0, nsamples %llu))",
+                    who, (long long)nframes, (long long)p->first_start, (unsigned long long)in->frame_stride,
+                    (unsigned long long)in->nsamples);
+            return VIT_ERR_ARG;
+        }
+    }
+    if (nframes == 0) return VIT_OK;
+    hipError_t e = vit_launch_ofdm_sync(*in, *p, d_prs, nframes, d_start_out, d_rot_out, d_info, (hipStream_t)stream);
+    if (e != hipSuccess) { set_err("OFDM synchronisation launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
+    return VIT_OK;
+}
+
 void vit_sort_descs(vit_frame_desc* h_desc, int64_t nframes) {
     if (!h_desc || nframes <= 1) return;
     std::stable_sort(h_desc, h_desc + nframes,

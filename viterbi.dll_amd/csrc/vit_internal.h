@@ -106,6 +106,9 @@ hipError_t vit_launch_ofdm_fft(const vit_iq_input& in, uint32_t nfft, uint32_t n
                                uint64_t out_sym_stride, uint64_t out_frame_stride, hipStream_t stream);
 hipError_t vit_launch_ofdm_demod(const vit_iq_input& in, const uint16_t* d_bins, const vit_ofdm_shape& shape, float gain,
                                  int64_t nframes, uint8_t* d_fic, const vit_cif_ring* ring, uint64_t col, hipStream_t stream);
+// From the coarse start (vit_ofdm_sync.hip): one workgroup per frame; the caller has checked every argument rule.
+hipError_t vit_launch_ofdm_sync(const vit_iq_input& in, const vit_sync_params& p, const float* d_prs, int64_t nframes,
+                                int64_t* d_start_out, uint32_t* d_rot_out, uint32_t* d_info, hipStream_t stream);
 // After the decoder (vit_dab.hip).  The energy dispersal PRBS of one frame, (framebits+7)/8 bytes, padding bits 0
 // (framebits even, <= 9216; the caller checks).
 int64_t vit_prbs_bytes_host(uint8_t* h_out, uint32_t framebits);

@@ -23,12 +23,12 @@
 #include <cfloat>
 #include <cmath>
 
+#include "vit_fft_dev.h"
 #include "vit_internal.h"
 
 namespace {
 
-typedef uint32_t u32;
-typedef uint64_t u64;
+using namespace vit_fft;
 constexpr u32 RUN_MAX = 25;  // data symbols per workgroup at most: one extra transform per run is then <= 4 %
 
 struct TdArgs {
@@ -54,93 +54,6 @@ struct TdArgs {
 };
 
 
-// LDS index of point i.  Rows of 32 points are skewed by 4, rows of 256 by 1 more: the strided loads of the passes
-// (stride 2^s points between a thread's own, consecutive or 8 << s apart between lanes) and the bit-reversed stores of
-// the first pass (2^(m-5) apart between lanes) then spread over the 32 eight-byte bank pairs.
-constexpr u32 pad(u32 i) { return i + ((i >> 5) << 2) + (i >> 8); }
-// Point q of a thread's group in the pass behind s stages is base + (q << s), base = pass_base(T, s).  Its LDS index is
-// pad(base) + pad(q << s): the skew of a group's points does not depend on the thread, so one address register and
-// immediate offsets serve a pass (pad_is_affine checks it for every thread at compile time).
-constexpr u32 pass_base(u32 T, u32 s) { return ((T >> s) << (s + 3u)) + (T & ((1u << s) - 1u)); }
-constexpr bool pad_is_affine(u32 M) {
-    const u32 R1 = M % 3u ? M % 3u : 3u;
-    for (u32 s = R1; s < M; s += 3u)
-        for (u32 T = 0; T < (1u << M) / 8u; T++)
-            for (u32 q = 0; q < 8u; q++)
-                if (pad(pass_base(T, s) + (q << s)) != pad(pass_base(T, s)) + pad(q << s)) return false;
-    for (u32 i = 0; i < (1u << M); i++)  // the first pass stores aligned groups of at most 8 consecutive points
-        if (pad(i) != pad(i & ~7u) + (i & 7u)) return false;
-    return true;
-}
-
-template <u32 M>
-struct Cfg {
-    static constexpr u32 N = 1u << M;
-    static constexpr u32 TA = N / 8u;                  // threads that work on a symbol
-    static constexpr u32 TPB = TA < 64u ? 64u : TA;
-    static constexpr u32 R1 = M % 3u ? M % 3u : 3u;    // stages of the first pass
-    static constexpr u32 NP = (M - R1) / 3u;           // radix-8 passes behind it
-    // wavefronts per SIMD the registers are budgeted for: with rotation the prefetched phasors take 16 more (a workgroup
-    // of 1024 needs 4 in any case)
-    static constexpr u32 waves(bool rot) { return TPB == 1024u ? 4u : rot ? 3u : 4u; }
-    static constexpr u32 PADN = pad(N - 1u) + 1u;       // float2 of LDS for a symbol, then twpad(N/2 - 1) + 1 twiddles
-    static constexpr u32 LDS_BYTES = (PADN + N / 2u + N / 64u) * 8u;
-    static constexpr u32 CG = 2u;                      // groups of 4 carriers per thread: K <= N = 8 TA
-};
-
-__device__ __forceinline__ void bfly(float2& u, float2& v, float2 w) {
-    const float tr = w.x * v.x - w.y * v.y;
-    const float ti = w.x * v.y + w.y * v.x;
-    const float2 a = u;
-    u = make_float2(a.x + tr, a.y + ti);
-    v = make_float2(a.x - tr, a.y - ti);
-}
-__device__ __forceinline__ void bfly_one(float2& u, float2& v) {  // w = 1
-    const float2 a = u, t = v;
-    u = make_float2(a.x + t.x, a.y + t.y);
-    v = make_float2(a.x - t.x, a.y - t.y);
-}
-__device__ __forceinline__ void bfly_mj(float2& u, float2& v) {  // w = -j: t = (v.im, -v.re)
-    const float2 a = u, t = v;
-    u = make_float2(a.x + t.y, a.y - t.x);
-    v = make_float2(a.x - t.y, a.y + t.x);
-}
-
-// 3 stages on 8 points; w[h - 1 + jq]: the twiddle of stage h = 1, 2, 4 for the points q with q mod h = jq
-__device__ __forceinline__ void radix8(float2 (&v)[8], const float2 (&w)[7]) {
-#pragma unroll
-    for (u32 h = 1; h < 8; h *= 2)
-#pragma unroll
-        for (u32 q = 0; q < 8; q++)
-            if (!(q & h)) bfly(v[q], v[q + h], w[h - 1 + (q & (h - 1))]);
-}
-
-// stages 1 ... R1 on the 2^R1 points of one group of the first pass; e1, e3: the twiddles at 1/8 and 3/8 of a half turn
-template <u32 R1>
-__device__ __forceinline__ void first_stages(float2* v, float2 e1, float2 e3) {
-#pragma unroll
-    for (u32 q = 0; q < (1u << R1); q += 2) bfly_one(v[q], v[q + 1]);
-    if (R1 >= 2) {
-#pragma unroll
-        for (u32 q = 0; q < (1u << R1); q += 4) {
-            bfly_one(v[q], v[q + 2]);
-            bfly_mj(v[q + 1], v[q + 3]);
-        }
-    }
-    if (R1 >= 3) {
-        bfly_one(v[0], v[4]);
-        bfly(v[1], v[5], e1);
-        bfly_mj(v[2], v[6]);
-        bfly(v[3], v[7], e3);
-    }
-}
-
-constexpr u32 bitrev(u32 x, u32 bits) {
-    u32 r = 0;
-    for (u32 b = 0; b < bits; b++) r |= (x >> b & 1u) << (bits - 1u - b);
-    return r;
-}
-
 // the two soft bytes of one carrier (low byte: bit n, next byte: bit n + K) from a = z[l], b = z[l-1]: vit_ofdm.hip's
 __device__ __forceinline__ u32 soft_pair(float ar, float ai, float br, float bi, float gain) {
     const float re = ar * br + ai * bi;
@@ -154,19 +67,6 @@ __device__ __forceinline__ u32 soft_pair(float ar, float ai, float br, float bi,
         q = (u32)q0 | (u32)q1 << 8;
     }
     return q;
-}
-
-// LDS index of twiddle k: the lanes of a pass read twiddles a power of two apart
-constexpr u32 twpad(u32 k) { return k + (k >> 5); }
-
-// the 7 twiddles of thread T's group in the pass behind s stages, in radix8's order, from the LDS copy of the table
-template <u32 M>
-__device__ __forceinline__ void load_twiddles(const float2* tw, u32 T, u32 s, float2 (&w)[7]) {
-    const u32 j0 = T & ((1u << s) - 1u);
-#pragma unroll
-    for (u32 a = 0; a < 3; a++)
-#pragma unroll
-        for (u32 jq = 0; jq < (1u << a); jq++) w[(1u << a) - 1u + jq] = tw[twpad((j0 + (jq << s)) * ((1u << M) >> (s + a + 1u)))];
 }
 
 template <u32 M, bool ROT>
