@@ -273,6 +273,46 @@ int vit_dabplus_punctured_superframes_dev(const uint8_t *d_in, const vit_punct_p
                                           int32_t *d_ret, uint8_t *d_fire_ok, uint32_t RSDims,
                                           int64_t nsf, void *stream);
 
+/* DAB+ access units (TS 102 563 clause 5.2): what the audio decoder consumes.  Built-in definition, on a superframe of
+ * L = 110*RSDims bytes in natural order (the layout of d_rs_out), RSDims 1 ... 48:
+ *   bytes 0..1             the fire code over bytes 2..10, as above
+ *   byte 2                 bit 7 rfa, bit 6 dac_rate, bit 5 sbr_flag, bit 4 aac_channel_mode, bit 3 ps_flag,
+ *                          bits 2..0 mpeg_surround_config
+ *   num_aus                from (dac_rate, sbr_flag): (0,1) -> 2, (1,1) -> 3, (0,0) -> 4, (1,0) -> 6
+ *   au_start[0]            the header's length: 5, 6, 8 or 11 bytes for num_aus 2, 3, 4 or 6
+ *   au_start[1..num_aus-1] 12-bit big-endian fields packed from byte 3 on (four padding bits follow when num_aus is 2
+ *                          or 4): au_start[1] = b3<<4 | b4>>4, au_start[2] = (b4&15)<<8 | b5,
+ *                          au_start[3] = b6<<4 | b7>>4, au_start[4] = (b7&15)<<8 | b8, au_start[5] = b9<<4 | b10>>4
+ *   au_start[num_aus]      L
+ *   header validity        the library's rule: au_start[n+1] - au_start[n] >= 3 for every n in 0 ... num_aus-1, that is
+ *                          strictly increasing, inside the superframe, and at least one byte in front of each CRC
+ *   AU n                   bytes au_start[n] ... au_start[n+1]-1; its last two bytes hold the ones' complement of the
+ *                          CRC-16 of the FIB check (0x1021, preset 0xFFFF, MSB first) over all the bytes before them
+ * Example: byte 2 = 0x00 and bytes 3..7 = 12 34 56 78 90 give 4 AUs starting at 8, 0x123, 0x456 and 0x789. */
+#define VIT_AU_OK 0          /* header parsed and valid; crc_ok is meaningful */
+#define VIT_AU_RS_FAILED 1   /* d_ret[s] < 0: superframe not read, every other field 0 */
+#define VIT_AU_BAD_HEADER 2  /* au_start rule violated: num_aus, param, fire_ok and au_start as parsed, crc_ok 0 */
+typedef struct vit_au_table {   /* 20 bytes, one per superframe */
+    uint8_t  status, num_aus, param /* byte 2 */, crc_ok /* bit n: AU n's CRC holds */;
+    uint16_t au_start[7];       /* [0 .. num_aus]; unused entries 0 */
+    uint8_t  fire_ok, reserved; /* fire code recomputed on the bytes given (after RS: on the corrected ones) */
+} vit_au_table;
+/* Superframe s lies at d_sf + s*sf_stride, sf_stride >= 110*RSDims; base pointer and stride may have any alignment,
+ * d_au must be 4-byte aligned.  d_sf is only read, and no byte outside a superframe's own L bytes is read; every record
+ * is written completely (reserved = 0).  d_ret (may be NULL) is the RS return value per superframe: a negative one gives
+ * VIT_AU_RS_FAILED.  sf_stride = 110*RSDims reads d_rs_out of the DAB+ chains (on the same stream, after the chain
+ * call); sf_stride = 120*RSDims with d_ret = NULL reads the first 110 rows of d_work, the superframe before RS, whose
+ * AUs with a good CRC are usable even where RS gave up on a column.  One wavefront per superframe; errors as above. */
+int vit_dabplus_aus_dev(const uint8_t *d_sf, uint64_t sf_stride, uint32_t RSDims, int64_t nsf,
+                        const int32_t *d_ret, vit_au_table *d_au, void *stream);
+/* Host only, needs no GPU: the same definition for one superframe (no RS gating).  VIT_ERR_ARG for a NULL pointer or
+ * RSDims outside 1 ... 48. */
+int vit_dabplus_aus_host(const uint8_t *h_sf, uint32_t RSDims, vit_au_table *h_out);
+/* d_ok[i] = 1 if bytes 0..1 at d_bytes + i*stride equal the fire remainder of bytes 2..10 there, else 0 (n candidates,
+ * 11 bytes read of each, any alignment).  With stride = 24*RSDims over descrambled decoded frames (d_work) every logical
+ * frame is tested as a superframe start in one call. */
+int vit_fire_code_dev(const uint8_t *d_bytes, uint64_t stride, int64_t n, uint8_t *d_ok, void *stream);
+
 /* From the CIF stream: MSC time de-interleaving (EN 300 401 clause 12).  Every MSC sub-channel (DAB and DAB+ audio,
  * data; not the FIC) is spread over 16 logical frames, so a CIF carries one sixteenth of each of 16 logical frames.
  * Built-in definition:

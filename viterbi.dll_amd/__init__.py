@@ -28,6 +28,7 @@ EXPORTS = [
     "vit_punctured_length", "vit_decode_punctured_dev", "vit_decode_punctured_varlen_dev",
     "vit_energy_dispersal_prbs", "vit_energy_dispersal_dev", "vit_energy_dispersal_varlen_dev", "vit_fib_crc_dev",
     "vit_decode_fic_dev", "vit_dabplus_punctured_superframes_dev",
+    "vit_dabplus_aus_dev", "vit_dabplus_aus_host", "vit_fire_code_dev",
     "vit_time_deinterleave_dev", "vit_decode_punctured_ti_dev", "vit_dabplus_ti_superframes_dev",
     "vit_freq_interleave_bins", "vit_ofdm_demap_dev",
     "vit_fft_twiddles", "vit_nco_table", "vit_ofdm_fft_dev", "vit_ofdm_demod_dev", "vit_ofdm_sync_dev",
@@ -47,6 +48,11 @@ class FrameDesc(C.Structure):
 
 
 DESC_DTYPE = np.dtype([("sym_offset", "<u8"), ("out_offset", "<u8"), ("framebits", "<u4"), ("reserved", "<u4")])
+
+# vit_au_table of include/viterbi_amd.h: one record per DAB+ superframe
+AU_DTYPE = np.dtype([("status", "u1"), ("num_aus", "u1"), ("param", "u1"), ("crc_ok", "u1"), ("au_start", "<u2", (7,)),
+                     ("fire_ok", "u1"), ("reserved", "u1")])
+AU_OK, AU_RS_FAILED, AU_BAD_HEADER = 0, 1, 2
 
 PUNCT_MAX_SEGS = 8
 
@@ -147,6 +153,9 @@ def lib():
         L.vit_decode_fic_dev.argtypes = [vp, vp, vp, C.c_uint32, C.c_int64, C.POINTER(PunctProfile), C.c_uint8, vp]
         L.vit_dabplus_punctured_superframes_dev.argtypes = [vp, C.POINTER(PunctProfile), C.c_uint8, vp, vp, vp, vp,
                                                             C.c_uint32, C.c_int64, vp]
+        L.vit_dabplus_aus_dev.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_int64, vp, vp, vp]
+        L.vit_dabplus_aus_host.argtypes = [vp, C.c_uint32, vp]
+        L.vit_fire_code_dev.argtypes = [vp, C.c_uint64, C.c_int64, vp, vp]
         pr, pp = C.POINTER(CifRing), C.POINTER(PunctProfile)
         L.vit_time_deinterleave_dev.argtypes = [pr, C.c_uint64, C.c_uint32, vp, C.c_int64, vp]
         L.vit_decode_punctured_ti_dev.argtypes = [pr, C.c_uint64, vp, C.c_uint32, C.c_int64, pp, C.c_uint8, vp]
@@ -435,6 +444,30 @@ def dabplus_punctured_superframes_dev(d_in, profile, d_work, d_rs_out, d_ret, RS
     _check(lib().vit_dabplus_punctured_superframes_dev(_ptr(d_in), _profile_ref(profile), int(erasure), _ptr(d_work),
                                                        _ptr(d_rs_out), _ptr(d_ret), _ptr(d_fire_ok), RSDims, nsf,
                                                        _stream_ptr(stream)), "vit_dabplus_punctured_superframes_dev")
+
+
+def dabplus_aus_dev(d_sf, RSDims, nsf, d_au, d_ret=None, sf_stride=None, stream=None):
+    """one AU_DTYPE record (20 bytes, in the uint8 tensor d_au) per superframe of 110*RSDims bytes at d_sf + s*sf_stride
+    (default: back to back, the layout of d_rs_out); d_ret: the chain's RS return values, negative -> AU_RS_FAILED.
+    sf_stride = 120*RSDims on d_work reads the superframes before RS."""
+    _check(lib().vit_dabplus_aus_dev(_ptr(d_sf), 110 * RSDims if sf_stride is None else sf_stride, RSDims, nsf,
+                                     _ptr(d_ret), _ptr(d_au), _stream_ptr(stream)), "vit_dabplus_aus_dev")
+
+
+def dabplus_aus_host(sf, RSDims):
+    """host, no GPU: the AU_DTYPE record of one superframe (110*RSDims bytes)"""
+    sf = np.ascontiguousarray(sf, np.uint8).reshape(-1)
+    if sf.size != 110 * RSDims:
+        raise ValueError("a superframe has 110*RSDims bytes")
+    out = np.zeros(1, AU_DTYPE)
+    _check(lib().vit_dabplus_aus_host(_np(sf), RSDims, _np(out)), "vit_dabplus_aus_host")
+    return out[0]
+
+
+def fire_code_dev(d_bytes, stride, n, d_ok, stream=None):
+    """d_ok[i] = the fire code of the 11 bytes at d_bytes + i*stride (stride 24*RSDims over descrambled frames: every
+    logical frame as a candidate superframe start)"""
+    _check(lib().vit_fire_code_dev(_ptr(d_bytes), stride, n, _ptr(d_ok), _stream_ptr(stream)), "vit_fire_code_dev")
 
 
 def cif_ring(d_ring, first_row):

@@ -1198,6 +1198,41 @@ int vit_dabplus_punctured_superframes_dev(const uint8_t* d_in, const vit_punct_p
                          d_ret, d_fire_ok, RSDims, nsf, stream);
 }
 
+// ---- DAB+ access units: superframe header and AU CRCs, per-frame fire code (vit_dab.hip) ----------------------------
+int vit_dabplus_aus_dev(const uint8_t* d_sf, uint64_t sf_stride, uint32_t RSDims, int64_t nsf, const int32_t* d_ret,
+                        vit_au_table* d_au, void* stream) {
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (RSDims == 0 || RSDims > 48u || nsf < 0 || sf_stride < 110ull * RSDims ||
+        (nsf > 0 && (!d_sf || !d_au || (reinterpret_cast<uintptr_t>(d_au) & 3u)))) {
+        set_err("vit_dabplus_aus_dev: bad arguments (RSDims=%u, 1 ... 48; nsf=%lld; sf_stride=%llu, >= 110*RSDims; d_au "
+                "4-byte aligned)", RSDims, (long long)nsf, (unsigned long long)sf_stride);
+        return VIT_ERR_ARG;
+    }
+    hipError_t e = vit_launch_aus(d_sf, sf_stride, RSDims, nsf, d_ret, d_au, (hipStream_t)stream);
+    if (e != hipSuccess) { set_err("access unit launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
+    return VIT_OK;
+}
+
+int vit_dabplus_aus_host(const uint8_t* h_sf, uint32_t RSDims, vit_au_table* h_out) {
+    if (!h_sf || !h_out || RSDims == 0 || RSDims > 48u) {
+        set_err("vit_dabplus_aus_host: bad arguments (RSDims=%u, 1 ... 48)", RSDims);
+        return VIT_ERR_ARG;
+    }
+    vit_au_table_host(h_sf, RSDims, h_out);
+    return VIT_OK;
+}
+
+int vit_fire_code_dev(const uint8_t* d_bytes, uint64_t stride, int64_t n, uint8_t* d_ok, void* stream) {
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (n < 0 || (n > 0 && (!d_bytes || !d_ok))) {
+        set_err("vit_fire_code_dev: bad arguments (n=%lld)", (long long)n);
+        return VIT_ERR_ARG;
+    }
+    hipError_t e = vit_launch_fire(d_bytes, stride, n, d_ok, (hipStream_t)stream);
+    if (e != hipSuccess) { set_err("fire code launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
+    return VIT_OK;
+}
+
 // ---- from the CIF stream: MSC time de-interleaving (vit_ti.hip) ---------------------------------------------------
 int vit_time_deinterleave_dev(const vit_cif_ring* ring, uint64_t col, uint32_t ncols, uint8_t* d_out, int64_t nframes,
                               void* stream) {

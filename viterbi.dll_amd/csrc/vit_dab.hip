@@ -125,7 +125,7 @@ __global__ __launch_bounds__(TPB) void vit_disperse_varlen_kernel(uint8_t* __res
 }
 
 // Fire code remainder of bytes 2..10 (register 0, MSB first)
-__device__ __forceinline__ u32 fire_remainder(const uint8_t* m9) {
+__host__ __device__ __forceinline__ u32 fire_remainder(const uint8_t* m9) {
     u32 r = 0;
     for (u32 k = 0; k < 9u; k++) {
         r ^= (u32)m9[k] << 8;
@@ -193,6 +193,189 @@ __global__ __launch_bounds__(TPB) void vit_fib_kernel(uint8_t* __restrict__ fibs
     }
 }
 
+// ---- DAB+ access units (TS 102 563 clause 5.2): superframe header, AU CRCs ---------------------------------------
+// CRC-16 0x1021 over one byte without a table: crc * x^8 + b * x^16 mod g
+__host__ __device__ constexpr u32 crc16_step(u32 crc, u32 b) {
+    u32 x = ((crc >> 8) ^ b) & 0xFFu;
+    x ^= x >> 4;
+    return ((crc << 8) ^ (x << 12) ^ (x << 5) ^ x) & 0xFFFFu;
+}
+static_assert(crc16_step(0, 1) == crc16_byte(1) && crc16_step(0, 0xA7) == crc16_byte(0xA7) && crc16_step(0x1234, 0) ==
+              (crc16_byte(0x12) ^ 0x3400u), "the table-less byte step is the table's");
+
+constexpr u32 AU_MAX_L = 110u * 48u;                // the longest superframe
+constexpr u32 AU_MAX_CHUNK = (AU_MAX_L + 63u) / 64u;  // bytes of one lane's chunk of the longest AU
+constexpr u32 AU_POW_N = 63u * AU_MAX_CHUNK + 1u;
+// x^(8e) mod g for e = 0 ... 63 * 83: what a chunk's remainder is multiplied by when e bytes follow it
+struct AuPowTab {
+    uint16_t v[AU_POW_N];
+};
+constexpr AuPowTab make_au_pow() {
+    AuPowTab t{};
+    u32 r = 1;
+    for (u32 e = 0; e < AU_POW_N; e++) {
+        t.v[e] = (uint16_t)r;
+        r = crc16_step(r, 0);
+    }
+    return t;
+}
+__device__ const AuPowTab d_au_pow = make_au_pow();
+// the fire code's remainder of a 72-bit message (bytes 2..10, MSB first) with only bit t set
+struct FireBitTab {
+    uint16_t v[72];
+};
+constexpr FireBitTab make_fire_bits() {
+    FireBitTab t{};
+    u32 r = 0x782Fu;  // x^16 mod g: the last bit
+    for (int k = 71; k >= 0; k--) {
+        t.v[k] = (uint16_t)r;
+        r = (r & 0x8000u) ? ((r << 1) ^ 0x782Fu) & 0xFFFFu : (r << 1) & 0xFFFFu;
+    }
+    return t;
+}
+__device__ const FireBitTab d_fire_bits = make_fire_bits();
+
+// The header of a superframe of L bytes from its bytes 2..10 (include/viterbi_amd.h): start[0 .. num_aus], unused
+// entries 0; valid when every AU has at least 3 bytes.
+struct AuHeader {
+    u32 num_aus, valid, start[7];
+};
+__host__ __device__ __forceinline__ AuHeader au_parse(const u32* b /* bytes 0..10 */, u32 L) {
+    AuHeader h;
+    const u32 dac = (b[2] >> 6) & 1u, sbr = (b[2] >> 5) & 1u;
+    h.num_aus = sbr ? (dac ? 3u : 2u) : (dac ? 6u : 4u);
+    const u32 f[7] = {sbr ? (dac ? 6u : 5u) : (dac ? 11u : 8u),
+                      b[3] << 4 | b[4] >> 4,
+                      (b[4] & 15u) << 8 | b[5],
+                      b[6] << 4 | b[7] >> 4,
+                      (b[7] & 15u) << 8 | b[8],
+                      b[9] << 4 | b[10] >> 4,
+                      0u};
+    h.valid = 1u;
+#pragma unroll
+    for (u32 n = 0; n < 7u; n++) h.start[n] = n < h.num_aus ? f[n] : n == h.num_aus ? L : 0u;
+#pragma unroll
+    for (u32 n = 0; n < 6u; n++)
+        if (n < h.num_aus && (int)h.start[n + 1] - (int)h.start[n] < 3) h.valid = 0u;
+    return h;
+}
+// The record as its five little-endian dwords
+__host__ __device__ __forceinline__ void au_record(u32* w, u32 status, const AuHeader& h, u32 param, u32 crc_ok, u32 fire_ok) {
+    w[0] = status | h.num_aus << 8 | param << 16 | crc_ok << 24;
+    w[1] = h.start[0] | h.start[1] << 16;
+    w[2] = h.start[2] | h.start[3] << 16;
+    w[3] = h.start[4] | h.start[5] << 16;
+    w[4] = h.start[6] | fire_ok << 16;
+}
+
+// XOR over the wavefront, the result in every lane: two quad permutes, the two row mirrors, then the rows' results
+// collected in lane 63 by row_bcast15 / row_bcast31
+__device__ __forceinline__ u32 wave_xor(u32 v) {
+    v ^= (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
+    v ^= (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
+    v ^= (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false);  // row_half_mirror
+    v ^= (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false);  // row_mirror
+    v ^= (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);  // row_bcast15 into rows 1 and 3
+    v ^= (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);  // row_bcast31 into rows 2 and 3
+    return (u32)__builtin_amdgcn_readlane((int)v, 63);
+}
+
+// One wavefront per superframe, AU_WPB per workgroup.  The superframe comes in as aligned 16-byte windows (the windows
+// it shares with its neighbours byte by byte, so nothing outside its L bytes is read) into the wavefront's LDS image,
+// byte k at s[(p & 15) + k].  Header and fire code: lane t takes message bit t (and lanes 0..7 bits 64..71) times the
+// bit's remainder, XORed over the wavefront.  Each AU: lane i takes the register-0 remainder r_i of the i-th of 64
+// chunks of c = ceil(len/64) bytes, right-aligned (the leading chunks of a short AU are empty or short; leading zeros
+// do not change a register-0 remainder), the lane that holds the AU's first byte starting from the preset 0xFFFF
+// instead of 0; the AU's CRC register is XOR_i r_i * x^(8c(63-i)) mod g: one carry-less 16 x 16 multiply per lane by
+// d_au_pow[c(63-i)], an XOR over the wavefront of the 31-bit products, one reduction mod g.
+constexpr u32 AU_WPB = TPB / WAVE;
+__host__ __device__ constexpr u32 au_lds_bytes(u32 L) { return ((L + 30u) >> 4) << 4; }  // windows of (15 + L) bytes
+
+__global__ __launch_bounds__(TPB) void vit_au_kernel(const uint8_t* __restrict__ sf, u64 stride, u32 rsdims, long long nsf,
+                                                     const int32_t* __restrict__ ret, u32* __restrict__ au) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t s_au[];
+    const u32 lane = threadIdx.x & (WAVE - 1u), wave = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+    const u32 L = 110u * rsdims;
+    uint8_t* s = s_au + wave * au_lds_bytes(L);
+    const u32 fbit = d_fire_bits.v[lane], fbit2 = lane < 8u ? d_fire_bits.v[64u + lane] : 0u;
+    // every wavefront of a workgroup makes the same number of rounds: the barriers order the LDS image's writes and reads
+    for (long long f0 = (long long)blockIdx.x * AU_WPB; f0 < nsf; f0 += (long long)gridDim.x * AU_WPB) {
+        const long long f = f0 + wave;
+        const bool live = f < nsf;                                  // wave-uniform
+        const bool read = live && !(ret && ret[live ? f : 0] < 0);  // RS gave up: the superframe is not read
+        const uint8_t* p = sf + (u64)(live ? f : 0) * stride;
+        const u32 a = (u32)(reinterpret_cast<uintptr_t>(p) & 15u);
+        if (read) {
+            const u32 nwin = (a + L + 15u) >> 4;
+            for (u32 w = lane; w < nwin; w += WAVE) {
+                const int o = (int)(16u * w) - (int)a;
+                if (o >= 0 && (u32)o + 16u <= L) {
+                    *reinterpret_cast<uint4*>(s + 16u * w) = *reinterpret_cast<const uint4*>(p + o);
+                } else {
+                    for (u32 j = 0; j < 16u; j++) {
+                        const int k = o + (int)j;
+                        if (k >= 0 && (u32)k < L) s[16u * w + j] = p[k];
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        if (read) {
+            const uint8_t* m = s + a;  // the superframe's byte 0
+            // bytes 0..10 into scalars through lanes 0..10
+            const u32 hb = m[lane < 11u ? lane : 0u];
+            u32 b[11];
+#pragma unroll
+            for (u32 k = 0; k < 11u; k++) b[k] = (u32)__builtin_amdgcn_readlane((int)hb, k);
+            const AuHeader h = au_parse(b, L);
+            u32 fv = ((m[2u + (lane >> 3)] >> (7u - (lane & 7u))) & 1u) ? fbit : 0u;
+            fv ^= ((b[10] >> (7u - (lane & 7u))) & 1u) ? fbit2 : 0u;
+            const u32 fire_ok = wave_xor(fv) == (b[0] << 8 | b[1]) ? 1u : 0u;
+            u32 crc_ok = 0;
+            if (h.valid) {
+#pragma unroll
+                for (u32 n = 0; n < 6u; n++) {
+                    if (n >= h.num_aus) break;  // wave-uniform
+                    const u32 len = h.start[n + 1] - h.start[n] - 2u;  // >= 1 bytes under the CRC
+                    const uint8_t* q = m + h.start[n];
+                    const u32 c = (len + 63u) >> 6;
+                    const int lo = (int)len - (int)((64u - lane) * c), hi = lo + (int)c;
+                    u32 r = (lo <= 0 && hi > 0) ? 0xFFFFu : 0u;
+                    for (int k = lo > 0 ? lo : 0; k < hi; k++) r = crc16_step(r, q[k]);
+                    const u32 x = d_au_pow.v[(63u - lane) * c];
+                    u32 prod = 0;
+#pragma unroll
+                    for (u32 j = 0; j < 16u; j++) prod ^= ((x >> j) & 1u) ? r << j : 0u;
+                    prod = wave_xor(prod);
+                    const u32 crc = (prod & 0xFFFFu) ^ crc16_step(crc16_step(prod >> 16, 0), 0);
+                    const u32 stored = (u32)q[len] << 8 | q[len + 1u];
+                    if ((crc ^ 0xFFFFu) == stored) crc_ok |= 1u << n;
+                }
+            }
+            if (lane < 5u) {
+                u32 w[5];
+                au_record(w, h.valid ? VIT_AU_OK : VIT_AU_BAD_HEADER, h, b[2], crc_ok, fire_ok);
+                au[5u * (u64)f + lane] = lane == 0u ? w[0] : lane == 1u ? w[1] : lane == 2u ? w[2] : lane == 3u ? w[3] : w[4];
+            }
+        } else if (live && lane < 5u) {
+            au[5u * (u64)f + lane] = lane == 0u ? (u32)VIT_AU_RS_FAILED : 0u;
+        }
+        __syncthreads();  // the image is read before the next round overwrites it
+    }
+}
+
+// One lane per candidate: bytes 0..1 at bytes + i*stride against the fire remainder of bytes 2..10 there
+__global__ __launch_bounds__(TPB) void vit_fire_kernel(const uint8_t* __restrict__ bytes, u64 stride, long long n,
+                                                       uint8_t* __restrict__ ok) {
+    for (long long i = (long long)blockIdx.x * TPB + threadIdx.x; i < n; i += (long long)gridDim.x * TPB) {
+        const uint8_t* p = bytes + (u64)i * stride;
+        uint8_t b[11];
+#pragma unroll
+        for (u32 k = 0; k < 11u; k++) b[k] = p[k];
+        ok[i] = fire_remainder(b + 2) == ((u32)b[0] << 8 | b[1]) ? 1 : 0;
+    }
+}
+
 unsigned grid_for(long long items, u32 per_block) {
     const long long b = (items + per_block - 1) / per_block;
     return (unsigned)(b < (1 << 20) ? b : (1 << 20));
@@ -235,5 +418,37 @@ hipError_t vit_launch_dabplus_post(uint8_t* d_work, uint32_t rsdims, int64_t nsf
     const long long nframes = 5ll * nsf;
     hipLaunchKernelGGL(vit_dabplus_post_kernel, dim3(grid_for(nframes, TPB / WAVE)), dim3(TPB), 0, stream, d_work, rsdims,
                        nframes, d_fire_ok);
+    return hipGetLastError();
+}
+
+void vit_au_table_host(const uint8_t* h_sf, uint32_t rsdims, vit_au_table* h_out) {
+    const u32 L = 110u * rsdims;
+    u32 b[11];
+    for (u32 k = 0; k < 11u; k++) b[k] = h_sf[k];
+    const AuHeader h = au_parse(b, L);
+    u32 crc_ok = 0;
+    for (u32 n = 0; h.valid && n < h.num_aus; n++) {
+        u32 r = 0xFFFFu;
+        for (u32 k = h.start[n]; k < h.start[n + 1] - 2u; k++) r = crc16_step(r, h_sf[k]);
+        if ((r ^ 0xFFFFu) == ((u32)h_sf[h.start[n + 1] - 2u] << 8 | h_sf[h.start[n + 1] - 1u])) crc_ok |= 1u << n;
+    }
+    u32 w[5];
+    au_record(w, h.valid ? VIT_AU_OK : VIT_AU_BAD_HEADER, h, b[2], crc_ok,
+              fire_remainder(h_sf + 2) == (b[0] << 8 | b[1]) ? 1u : 0u);
+    uint8_t* o = reinterpret_cast<uint8_t*>(h_out);
+    for (u32 k = 0; k < 20u; k++) o[k] = (uint8_t)(w[k >> 2] >> (8u * (k & 3u)));
+}
+
+hipError_t vit_launch_aus(const uint8_t* d_sf, uint64_t sf_stride, uint32_t rsdims, int64_t nsf, const int32_t* d_ret,
+                          vit_au_table* d_au, hipStream_t stream) {
+    if (nsf <= 0) return hipSuccess;
+    hipLaunchKernelGGL(vit_au_kernel, dim3(grid_for(nsf, AU_WPB)), dim3(TPB), AU_WPB * au_lds_bytes(110u * rsdims), stream,
+                       d_sf, (u64)sf_stride, rsdims, (long long)nsf, d_ret, reinterpret_cast<u32*>(d_au));
+    return hipGetLastError();
+}
+
+hipError_t vit_launch_fire(const uint8_t* d_bytes, uint64_t stride, int64_t n, uint8_t* d_ok, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(vit_fire_kernel, dim3(grid_for(n, TPB)), dim3(TPB), 0, stream, d_bytes, (u64)stride, (long long)n, d_ok);
     return hipGetLastError();
 }

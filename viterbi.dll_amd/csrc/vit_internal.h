@@ -125,6 +125,13 @@ hipError_t vit_launch_fibs(uint8_t* d_fibs, int64_t nfibs, uint32_t fibs_per_fra
 // DAB+: 5*nsf frames of 24*rsdims bytes descrambled in place; d_fire_ok[s] (optional) = the fire code of superframe s
 // on its descrambled bytes 0..10.
 hipError_t vit_launch_dabplus_post(uint8_t* d_work, uint32_t rsdims, int64_t nsf, uint8_t* d_fire_ok, hipStream_t stream);
+// DAB+ access units: one vit_au_table per superframe of 110*rsdims bytes at d_sf + s*sf_stride (d_ret optional: a
+// negative value gives VIT_AU_RS_FAILED without reading the superframe); the host form takes one superframe.
+hipError_t vit_launch_aus(const uint8_t* d_sf, uint64_t sf_stride, uint32_t rsdims, int64_t nsf, const int32_t* d_ret,
+                          vit_au_table* d_au, hipStream_t stream);
+void vit_au_table_host(const uint8_t* h_sf, uint32_t rsdims, vit_au_table* h_out);
+// d_ok[i] = the fire code of the 11 bytes at d_bytes + i*stride.
+hipError_t vit_launch_fire(const uint8_t* d_bytes, uint64_t stride, int64_t n, uint8_t* d_ok, hipStream_t stream);
 // RS(120,110) superframe check, one lane per column.
 // host_polls_ret (nsf == 1, rsdims <= 256): d_ret is host-visible and receives its value with system-scope release
 // semantics after the last output byte, so the host may spin on it instead of synchronising the stream.
