@@ -544,6 +544,14 @@ typedef struct vit_sync_params {
  * sample magnitudes up to 2^12 at every nfft.  Underflow is gradual: denormal results are kept, as IEEE arithmetic has
  * them.  All-zero samples are inside the domain: every comparison ties, m^ = -M, tau = 0, turn = 0.  Outside it the
  * frame's outputs are unspecified; nothing but the call's output words is written.
+ * One extension of that domain, for step A alone: a sample that no transform reads - one outside the window of step B,
+ * c - W ... c - W + nfft - 1, so a guard pair of symbols 1 ... cp_symbols - may have any finite value for which nothing
+ * overflows, magnitudes under 2^-40 and denormals included.  Step A multiplies samples with samples only and meets no
+ * table; gamma, E, q, the polynomial and turn are then what IEEE arithmetic gives, a denormal or zero q and a denormal
+ * turn among them.  Every sample inside the window of step B keeps the floor of "From the samples": 0 or 2^-40 and more.
+ * The accumulators start at +0, so gamma.im is never -0: gamma.re < 0 with gamma.im = 0 gives turn = +1/2 and
+ * step_frac * nfft = 2^31 mod 2^32; a gamma.im < 0 too small to change fl(0.5 - r) gives turn = -1/2.  thr may be any
+ * positive binary32 value, denormal included; fl(thr * pmax) may be denormal, and where it rounds to 0, tau = 0.
  * Skip rule: a frame's reads are taken to span c - W ... c + (nsyms-1)*S + nfft - 1 + W.  With in->d_start given, a frame
  * whose span is not inside [0, nsamples) is skipped on the device: it gets start -1, rot {0, 0} and info zeros, so
  * vit_ofdm_demod_dev skips it too by its own rule.  Without in->d_start such a frame is VIT_ERR_ARG.

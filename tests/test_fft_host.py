@@ -109,11 +109,11 @@ def front_model(x, tw, nco=None, nco_bits=0, rot=None, sym_stride=None):
 
 def time_domain(z, guard, cfo=0.0):
     """(nframes, nsyms, nfft) spectra -> (nframes, nsyms*(guard + nfft)) complex128 samples: inverse FFT (scaled to unit
-    carriers), cyclic prefix of `guard` samples in front of every symbol, then a frequency offset of `cfo` carrier
-    spacings, continuous over the frame"""
+    carriers), cyclic prefix of `guard` samples (any length) in front of every symbol, then a frequency offset of `cfo`
+    carrier spacings, continuous over the frame"""
     nframes, nsyms, nfft = z.shape
     x = np.fft.ifft(np.asarray(z, np.complex128), axis=-1) * nfft
-    x = np.concatenate([x[..., nfft - guard:], x], axis=-1).reshape(nframes, -1)
+    x = x[..., np.arange(-guard, nfft) % nfft].reshape(nframes, -1)  # a guard longer than the symbol wraps around it
     n = np.arange(x.shape[1])
     return x * np.exp(2j * np.pi * cfo * n / nfft)[None, :]
 

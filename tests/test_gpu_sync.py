@@ -53,8 +53,11 @@ def directed(shape, nframes=8, uniform=False):
 
 
 def run_sync(V, x, prm, prs, coarse, nframes, table=True, alias=False, nco_bits=12, with_info=True, nsamples=None,
-             frame_stride=None):
-    """one call on guarded outputs; the whole buffers are compared with the model's image -> the model's outputs"""
+             frame_stride=None, unspecified=(), device=None):
+    """one call on guarded outputs; the whole buffers are compared with the model's image -> the model's outputs.
+    unspecified: frames outside the header's domain - the model skips them, their words are not compared except that
+    the start is an integer of c - W - backoff ... c + W - backoff (tau <= 2W), and the device's words are returned
+    for them.  device: a dict that gets the device's words, without the guards: start, rot (n, 2), info (n, 8)"""
     nfft = prm.nfft
     tw, d_tw = tw_tables(V, nfft)
     nco, d_nco = nco_tables(V, nco_bits)
@@ -78,7 +81,10 @@ def run_sync(V, x, prm, prs, coarse, nframes, table=True, alias=False, nco_bits=
                     nsamples=nsamples)
     torch.cuda.synchronize()
     n = x.size if nsamples is None else nsamples
-    start, rot, info, turn = sync_model(x[:n], coarse[:nframes], prm, prs, tw, nco, nco_bits)
+    bad = np.asarray(unspecified, np.int64)
+    model_coarse = np.array(coarse[:nframes], np.int64)
+    model_coarse[bad] = -1  # skipped by the model
+    start, rot, info, turn = sync_model(x[:n], model_coarse, prm, prs, tw, nco, nco_bits)
     want_so = np.full(so.numel(), SENT64, np.int64)
     want_so[GW:GW + nframes] = start
     want_ro = np.full(ro.numel(), SENT32, np.uint32)
@@ -87,6 +93,17 @@ def run_sync(V, x, prm, prs, coarse, nframes, table=True, alias=False, nco_bits=
     if with_info:
         want_io[5:5 + 8 * nframes] = info.reshape(-1)
     got_so, got_ro, got_io = so.cpu().numpy(), ro.cpu().numpy().view(np.uint32), io.cpu().numpy().view(np.uint32)
+    if device is not None:
+        device.update(start=got_so[GW:GW + nframes].copy(), rot=got_ro[2 * GW:2 * GW + 2 * nframes].reshape(-1, 2).copy(),
+                      info=got_io[5:5 + 8 * nframes].reshape(-1, 8).copy())
+    for t in bad:
+        lo = int(coarse[t]) - prm.W - prm.backoff
+        assert lo <= int(got_so[GW + t]) <= lo + 2 * prm.W, "the start of a frame outside the domain"
+        start[t], rot[t] = got_so[GW + t], got_ro[2 * GW + 2 * t:2 * GW + 2 * t + 2]
+        want_so[GW + t], want_ro[2 * GW + 2 * t:2 * GW + 2 * t + 2] = start[t], rot[t]
+        if with_info:
+            info[t] = got_io[5 + 8 * t:13 + 8 * t]
+            got_io[5 + 8 * t:13 + 8 * t] = want_io[5 + 8 * t:13 + 8 * t]  # its floats may be NaN: not compared
     assert np.array_equal(got_so, want_so), "starts and their guards"
     assert np.array_equal(got_ro, want_ro), "rot and its guards"
     ints = np.zeros(io.numel(), bool)

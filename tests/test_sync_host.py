@@ -91,9 +91,10 @@ def join(re, im):
     return out
 
 
-def sync_model(x, coarse, prm, prs, tw, nco, nco_bits):
+def sync_model(x, coarse, prm, prs, tw, nco, nco_bits, detail=None):
     """x: the samples (complex64, 1-D); coarse: the frames' coarse starts -> (start int64 (n,), rot uint32 (n, 2), info
-    uint32 (n, 8), turn float32 (n,)); a frame whose span is outside the buffer gets -1, {0, 0}, zeros"""
+    uint32 (n, 8), turn float32 (n,)); a frame whose span is outside the buffer gets -1, {0, 0}, zeros.  detail: a list
+    that gets, per frame that is not skipped, a dict of the intermediate values t, step_frac, metric and p"""
     x = np.asarray(x, np.complex64)
     nfft, S, G, W, M = prm.nfft, prm.sym_stride, prm.guard, prm.W, prm.M
     nacc, Gw = nacc_of(nfft), G - 2 * W
@@ -141,6 +142,8 @@ def sync_model(x, coarse, prm, prs, tw, nco, nco_bits):
             info[t, :2] = np.array([mhat, tau], np.int32).view(np.uint32)
             info[t, 2:] = np.array([g_re, g_im, en, metric[best], pmax, psum], F32).view(np.uint32)
             turns[t] = turn
+            if detail is not None:
+                detail.append(dict(t=t, step_frac=step_frac, metric=metric, p=p))
     return start, rot, info, turns
 
 
