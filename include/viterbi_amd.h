@@ -429,9 +429,10 @@ int vit_ofdm_demap_dev(const float *d_fft, uint64_t sym_stride, uint64_t frame_s
  * part of symbol l of frame t is samples start_t + l*sym_stride ... + nfft - 1.  Nothing else is read: not the samples
  * between useful parts, not the null symbol.  Any sample position is allowed; only d_iq must be 8-byte aligned.
  * The two tables come from vit_ofdm_sync_dev ("From the coarse start", below) or from the caller's own estimator.
- * Out of scope: first acquisition (finding the null symbol), integer sample formats, resampling, channel-state weighting. */
+ * Integer samples as receivers deliver them go through the *_iq_dev calls ("Integer sample formats", below).
+ * Out of scope: first acquisition (finding the null symbol), resampling, channel-state weighting. */
 typedef struct vit_iq_input {
-    const float    *d_iq;         /* interleaved (re, im) float32 samples, 8-byte aligned */
+    const float    *d_iq;         /* interleaved (re, im) float32 samples, 8-byte aligned (*_iq_dev: samples of fmt->format) */
     uint64_t        nsamples;     /* complex samples in d_iq: nothing at or beyond it is read */
     uint64_t        sym_stride;   /* samples from one symbol's useful part to the next: nfft + guard (mode I 2552), >= nfft */
     uint64_t        frame_stride; /* frame t starts at sample t*frame_stride when d_start is NULL (mode I 196608) */
@@ -571,6 +572,46 @@ typedef struct vit_sync_params {
 #define VIT_SYNC_ATAN_C6  0x1.1c32c4p-10f
 int vit_ofdm_sync_dev(const vit_iq_input *in, const vit_sync_params *p, const float *d_prs, int64_t nframes,
                       int64_t *d_start_out, uint32_t *d_rot_out, uint32_t *d_info, void *stream);
+
+/* Integer sample formats: the front end reads the receiver's own buffer.  An RTL-SDR delivers unsigned 8-bit pairs, a
+ * HackRF signed 8-bit, Airspy, SDRplay and USRP signed 16-bit; the *_iq_dev calls read them where the existing calls read
+ * float32, so no float copy of the stream exists on the device.  in->d_iq then points at samples of the named format (the
+ * caller casts); nsamples, sym_stride, frame_stride, d_start and every position keep counting COMPLEX samples. */
+#define VIT_IQ_F32  0   /* interleaved float32 (re, im): what the existing calls read */
+#define VIT_IQ_CU8  1   /* bytes (I, Q), unsigned, offset 127.5 */
+#define VIT_IQ_CS8  2   /* bytes (I, Q), two's complement */
+#define VIT_IQ_CS16 3   /* int16 (I, Q), little endian */
+typedef struct vit_iq_format {
+    uint32_t format;      /* VIT_IQ_* */
+    float    scale;       /* integer formats: finite, 2^-32 <= scale <= 2^16; VIT_IQ_F32: ignored, not even validated */
+} vit_iq_format;
+/* Definition: one line in front of step 1 of "From the samples" and of step A of "From the coarse start".  The binary32
+ * value of a component is
+ *   CU8:  fl( (float)(2*b - 255) * scale )  for byte b: the integer -255 ... 255 is exact in binary32, so there is one
+ *         rounding; the usual (b - 127.5)/128 is scale = 2^-8.  No CU8 sample is ever 0.
+ *   CS8:  fl( (float)b * scale )            for the two's complement byte b
+ *   CS16: fl( (float)h * scale )            for the int16 h
+ *   F32:  the value itself.
+ * Everything downstream is the existing definition applied to these floats: the result of an *_iq_dev call equals, in
+ * every output bit, the result of the existing call on the converted floats, and with VIT_IQ_F32 it is the existing call.
+ * Domain: the scale's range keeps every nonzero component inside [2^-40, 2^40] for all three integer formats; the bound
+ * of 2^12 of vit_ofdm_sync_dev stays the caller's to respect.  All-zero CS8 / CS16 symbols are inside the domain.
+ * Arguments after fmt: exactly those of the call without _iq, with its rules, its read and skip rules counted in samples,
+ * and its guarantees.  In addition VIT_ERR_ARG (with vit_last_error()) for a NULL fmt, an unknown format, or - for an
+ * integer format - a scale outside its range (NaN included).  d_iq must be 4-byte aligned for the integer formats (8-byte
+ * for VIT_IQ_F32); sample positions stay arbitrary: a CU8 frame may start at an address that is 2 mod 4.  No byte outside
+ * the samples the float32 path would read influences an output, and nothing at or beyond nsamples is read.
+ * vit_iq_convert_dev writes the 2*nsamples floats of the definition to d_out (8-byte aligned), for callers who need the
+ * floats themselves (an estimator of their own, other consumers of vit_ofdm_fft_dev's input).  VIT_IQ_F32 is VIT_ERR_ARG:
+ * there is nothing to convert.  nsamples = 0 returns VIT_OK and writes nothing; enqueued on `stream` without synchronising. */
+int vit_ofdm_fft_iq_dev(const vit_iq_input *in, const vit_iq_format *fmt, uint32_t nfft, uint32_t nsyms, int64_t nframes,
+                        float *d_fft, uint64_t out_sym_stride, uint64_t out_frame_stride, void *stream);
+int vit_ofdm_demod_iq_dev(const vit_iq_input *in, const vit_iq_format *fmt, const uint16_t *d_bins,
+                          const vit_ofdm_shape *shape, float gain, int64_t nframes, uint8_t *d_fic,
+                          const vit_cif_ring *ring, uint64_t col, void *stream);
+int vit_ofdm_sync_iq_dev(const vit_iq_input *in, const vit_iq_format *fmt, const vit_sync_params *p, const float *d_prs,
+                         int64_t nframes, int64_t *d_start_out, uint32_t *d_rot_out, uint32_t *d_info, void *stream);
+int vit_iq_convert_dev(const void *d_iq, const vit_iq_format *fmt, uint64_t nsamples, float *d_out, void *stream);
 
 /* Kernel selection (the analogue of the reference's dispatcher, setupdll.cpp:195-270):
  *   0 = auto: launches of up to 2048 frames (they cannot fill the chip) take the latency kernel - one

@@ -32,6 +32,7 @@ EXPORTS = [
     "vit_time_deinterleave_dev", "vit_decode_punctured_ti_dev", "vit_dabplus_ti_superframes_dev",
     "vit_freq_interleave_bins", "vit_ofdm_demap_dev",
     "vit_fft_twiddles", "vit_nco_table", "vit_ofdm_fft_dev", "vit_ofdm_demod_dev", "vit_ofdm_sync_dev",
+    "vit_ofdm_fft_iq_dev", "vit_ofdm_demod_iq_dev", "vit_ofdm_sync_iq_dev", "vit_iq_convert_dev",
     "vit_decode_stream_multi",
 ]
 MULTI_LOOPBACK = 0x1
@@ -83,6 +84,16 @@ class IqInput(C.Structure):
     _fields_ = [("d_iq", C.c_void_p), ("nsamples", C.c_uint64), ("sym_stride", C.c_uint64), ("frame_stride", C.c_uint64),
                 ("d_start", C.c_void_p), ("d_tw", C.c_void_p), ("d_nco", C.c_void_p), ("nco_bits", C.c_uint32),
                 ("d_rot", C.c_void_p)]
+
+
+class IqFormat(C.Structure):
+    """vit_iq_format of include/viterbi_amd.h: IqFormat(format, scale)"""
+    _fields_ = [("format", C.c_uint32), ("scale", C.c_float)]
+
+
+# the sample formats of include/viterbi_amd.h (VIT_IQ_*) and the tensor types that hold them
+IQ_F32, IQ_CU8, IQ_CS8, IQ_CS16 = 0, 1, 2, 3
+_IQ_DTYPES = {IQ_CU8: "torch.uint8", IQ_CS8: "torch.int8", IQ_CS16: "torch.int16"}
 
 
 class SyncParams(C.Structure):
@@ -172,6 +183,11 @@ def lib():
         L.vit_ofdm_fft_dev.argtypes = [pi, C.c_uint32, C.c_uint32, C.c_int64, vp, C.c_uint64, C.c_uint64, vp]
         L.vit_ofdm_demod_dev.argtypes = [pi, vp, C.POINTER(OfdmShape), C.c_float, C.c_int64, vp, pr, C.c_uint64, vp]
         L.vit_ofdm_sync_dev.argtypes = [pi, C.POINTER(SyncParams), vp, C.c_int64, vp, vp, vp, vp]
+        pf = C.POINTER(IqFormat)
+        L.vit_ofdm_fft_iq_dev.argtypes = [pi, pf] + L.vit_ofdm_fft_dev.argtypes[1:]
+        L.vit_ofdm_demod_iq_dev.argtypes = [pi, pf] + L.vit_ofdm_demod_dev.argtypes[1:]
+        L.vit_ofdm_sync_iq_dev.argtypes = [pi, pf] + L.vit_ofdm_sync_dev.argtypes[1:]
+        L.vit_iq_convert_dev.argtypes = [vp, pf, C.c_uint64, vp, vp]
         _lib = L
     return _lib
 
@@ -565,20 +581,34 @@ def nco_table(bits):
     return out
 
 
-def iq_input(d_iq, d_tw, sym_stride, frame_stride=0, d_start=None, d_nco=None, nco_bits=0, d_rot=None, nsamples=None):
-    """device tensors -> IqInput.  d_iq: complex64 or (re, im)-interleaved float32 CUDA tensor; d_tw / d_nco: float32 CUDA
-    tensors from fft_twiddles / nco_table; d_start: int64 CUDA tensor of frame starts; d_rot: CUDA tensor of 4-byte
+def _iq_samples(d_iq, iq_format):
+    """complex samples a CUDA tensor of the format holds; ValueError for a tensor of another type"""
+    if iq_format == IQ_F32:
+        if not d_iq.is_cuda or str(d_iq.dtype) not in ("torch.complex64", "torch.float32"):
+            raise ValueError("d_iq must be a complex64 or float32 CUDA tensor")
+        return d_iq.numel() if str(d_iq.dtype) == "torch.complex64" else d_iq.numel() // 2
+    if iq_format not in _IQ_DTYPES:
+        raise ValueError("iq_format must be one of IQ_F32, IQ_CU8, IQ_CS8, IQ_CS16: %r" % (iq_format,))
+    if not d_iq.is_cuda or str(d_iq.dtype) != _IQ_DTYPES[iq_format]:
+        raise ValueError("d_iq must be a %s CUDA tensor of (I, Q) pairs for this iq_format" % _IQ_DTYPES[iq_format][6:])
+    return d_iq.numel() // 2
+
+
+def iq_input(d_iq, d_tw, sym_stride, frame_stride=0, d_start=None, d_nco=None, nco_bits=0, d_rot=None, nsamples=None,
+             iq_format=IQ_F32, iq_scale=1.0):
+    """device tensors -> IqInput.  d_iq: complex64 or (re, im)-interleaved float32 CUDA tensor - with iq_format IQ_CU8,
+    IQ_CS8 or IQ_CS16 a uint8, int8 or int16 CUDA tensor of (I, Q) pairs, for the *_iq_dev calls; d_tw / d_nco: float32
+    CUDA tensors from fft_twiddles / nco_table; d_start: int64 CUDA tensor of frame starts; d_rot: CUDA tensor of 4-byte
     elements, {phase0, step} per frame (torch has no uint32 arithmetic: upload a numpy uint32 array viewed as int32).
-    nsamples defaults to all of d_iq."""
-    if not d_iq.is_cuda or str(d_iq.dtype) not in ("torch.complex64", "torch.float32"):
-        raise ValueError("d_iq must be a complex64 or float32 CUDA tensor")
+    nsamples defaults to all of d_iq, counted in complex samples of its format.  iq_scale is not stored here: it travels
+    in the IqFormat of the call."""
+    total = _iq_samples(d_iq, iq_format)
     if not d_tw.is_cuda or str(d_tw.dtype) != "torch.float32" or (d_nco is not None and str(d_nco.dtype) != "torch.float32"):
         raise ValueError("d_tw and d_nco must be float32 CUDA tensors")
     if d_start is not None and (not d_start.is_cuda or str(d_start.dtype) != "torch.int64"):
         raise ValueError("d_start must be an int64 CUDA tensor")
     if d_rot is not None and (not d_rot.is_cuda or d_rot.element_size() != 4):
         raise ValueError("d_rot must be a CUDA tensor of 4-byte elements (uint32 pairs)")
-    total = d_iq.numel() if str(d_iq.dtype) == "torch.complex64" else d_iq.numel() // 2
     a = IqInput()
     a.d_iq = d_iq.data_ptr()
     a.nsamples = total if nsamples is None else int(nsamples)
@@ -592,51 +622,78 @@ def iq_input(d_iq, d_tw, sym_stride, frame_stride=0, d_start=None, d_nco=None, n
     return a
 
 
+def iq_convert_dev(d_iq, iq_format, iq_scale, d_out, nsamples=None, stream=None):
+    """Integer sample formats (include/viterbi_amd.h): the floats the front end makes of the samples, written to d_out
+    (complex64 or float32 CUDA tensor).  d_iq: uint8, int8 or int16 CUDA tensor of (I, Q) pairs as iq_format says;
+    nsamples defaults to all of d_iq."""
+    total = _iq_samples(d_iq, iq_format)
+    if not d_out.is_cuda or str(d_out.dtype) not in ("torch.complex64", "torch.float32"):
+        raise ValueError("d_out must be a complex64 or float32 CUDA tensor")
+    n = total if nsamples is None else int(nsamples)
+    if d_out.numel() * d_out.element_size() < 8 * n or n > total:
+        raise ValueError("d_iq and d_out must hold nsamples complex samples")
+    fmt = IqFormat(int(iq_format), float(iq_scale))
+    _check(lib().vit_iq_convert_dev(_ptr(d_iq), C.byref(fmt), n, _ptr(d_out), _stream_ptr(stream)), "vit_iq_convert_dev")
+
+
 def ofdm_fft_dev(d_iq, nfft, nsyms, nframes, d_tw, sym_stride, d_fft, frame_stride=None, d_start=None, d_nco=None,
-                 nco_bits=0, d_rot=None, out_sym_stride=None, out_frame_stride=None, stream=None, nsamples=None):
+                 nco_bits=0, d_rot=None, out_sym_stride=None, out_frame_stride=None, stream=None, nsamples=None,
+                 iq_format=IQ_F32, iq_scale=1.0):
     """From the samples (include/viterbi_amd.h): rotation and FFT of symbols 0 ... nsyms-1 of nframes frames into d_fft
     (complex64 or float32 CUDA tensor) in the layout ofdm_demap_dev reads.  Input arguments as iq_input; frame_stride is
     required unless d_start is given; the output strides count complex elements and default to nfft and
-    nsyms*out_sym_stride."""
+    nsyms*out_sym_stride.  With an integer iq_format (and its iq_scale) d_iq holds the receiver's own samples."""
     if not d_fft.is_cuda or str(d_fft.dtype) not in ("torch.complex64", "torch.float32"):
         raise ValueError("d_fft must be a complex64 or float32 CUDA tensor")
     if frame_stride is None and d_start is None:
         raise ValueError("frame_stride or d_start is required")
-    inp = iq_input(d_iq, d_tw, sym_stride, frame_stride, d_start, d_nco, nco_bits, d_rot, nsamples)
+    inp = iq_input(d_iq, d_tw, sym_stride, frame_stride, d_start, d_nco, nco_bits, d_rot, nsamples, iq_format)
     if out_sym_stride is None:
         out_sym_stride = int(nfft)
     if out_frame_stride is None:
         out_frame_stride = int(nsyms) * out_sym_stride
+    if iq_format != IQ_F32:
+        fmt = IqFormat(int(iq_format), float(iq_scale))
+        _check(lib().vit_ofdm_fft_iq_dev(C.byref(inp), C.byref(fmt), int(nfft), int(nsyms), nframes, _ptr(d_fft), out_sym_stride,
+                                         out_frame_stride, _stream_ptr(stream)), "vit_ofdm_fft_iq_dev")
+        return
     _check(lib().vit_ofdm_fft_dev(C.byref(inp), int(nfft), int(nsyms), nframes, _ptr(d_fft), out_sym_stride, out_frame_stride,
                                   _stream_ptr(stream)), "vit_ofdm_fft_dev")
 
 
 def ofdm_demod_dev(d_iq, shape, d_bins, gain, nframes, d_tw, sym_stride, frame_stride=None, d_start=None, d_nco=None,
-                   nco_bits=0, d_rot=None, d_fic=None, d_ring=None, first_row=0, col=0, stream=None, nsamples=None):
+                   nco_bits=0, d_rot=None, d_fic=None, d_ring=None, first_row=0, col=0, stream=None, nsamples=None,
+                   iq_format=IQ_F32, iq_scale=1.0):
     """From the samples (include/viterbi_amd.h): rotation, FFT and the demapping of ofdm_demap_dev in one kernel, no spectrum
     in memory.  Input arguments as iq_input (frame_stride is required unless d_start is given); shape, d_bins, gain,
-    d_fic, d_ring, first_row and col as ofdm_demap_dev."""
+    d_fic, d_ring, first_row and col as ofdm_demap_dev.  With an integer iq_format (and its iq_scale) d_iq holds the
+    receiver's own samples."""
     if not isinstance(shape, OfdmShape):
         shape = OfdmShape(*[int(v) for v in shape])
     if not d_bins.is_cuda or d_bins.element_size() != 2:
         raise ValueError("d_bins must be a CUDA tensor of 2-byte elements (uint16 bins)")
     if frame_stride is None and d_start is None:
         raise ValueError("frame_stride or d_start is required")
-    inp = iq_input(d_iq, d_tw, sym_stride, frame_stride, d_start, d_nco, nco_bits, d_rot, nsamples)
+    inp = iq_input(d_iq, d_tw, sym_stride, frame_stride, d_start, d_nco, nco_bits, d_rot, nsamples, iq_format)
     ring = None if d_ring is None else C.byref(cif_ring(d_ring, first_row))
+    if iq_format != IQ_F32:
+        fmt = IqFormat(int(iq_format), float(iq_scale))
+        _check(lib().vit_ofdm_demod_iq_dev(C.byref(inp), C.byref(fmt), _ptr(d_bins), C.byref(shape), float(gain), nframes,
+                                           _ptr(d_fic), ring, col, _stream_ptr(stream)), "vit_ofdm_demod_iq_dev")
+        return
     _check(lib().vit_ofdm_demod_dev(C.byref(inp), _ptr(d_bins), C.byref(shape), float(gain), nframes, _ptr(d_fic), ring, col,
                                     _stream_ptr(stream)), "vit_ofdm_demod_dev")
 
 
 def ofdm_sync_dev(d_iq, nfft, nsyms, nframes, d_tw, sym_stride, d_nco, nco_bits, d_prs, d_start_out, d_rot_out, W, M,
                   cp_symbols=None, thr=0.5, backoff=0, frame_stride=None, first_start=0, d_start=None, d_info=None,
-                  stream=None, nsamples=None):
+                  stream=None, nsamples=None, iq_format=IQ_F32, iq_scale=1.0):
     """From the coarse start (include/viterbi_amd.h): per frame the fine start and the carrier offset, written as the
     tables ofdm_demod_dev reads - d_start_out (int64 CUDA tensor, nframes) and d_rot_out (CUDA tensor of 4-byte elements,
     {0, step} per frame).  Input arguments as iq_input; the coarse starts are d_start (d_start_out may be the same
     tensor) or first_start + t*frame_stride.  d_prs: the transmitted phase reference symbol, nfft values in FFT order
     (complex64 or float32 CUDA tensor); cp_symbols defaults to nsyms - 1; d_info (optional): CUDA tensor of 4-byte
-    elements, 8 words per frame."""
+    elements, 8 words per frame.  With an integer iq_format (and its iq_scale) d_iq holds the receiver's own samples."""
     if d_nco is None:
         raise ValueError("d_nco is required")
     if frame_stride is None and d_start is None:
@@ -651,9 +708,14 @@ def ofdm_sync_dev(d_iq, nfft, nsyms, nframes, d_tw, sym_stride, d_nco, nco_bits,
         raise ValueError("d_rot_out must be a CUDA tensor of 2*nframes 4-byte elements (uint32 pairs)")
     if d_info is not None and (not d_info.is_cuda or d_info.element_size() != 4 or d_info.numel() < 8 * nframes):
         raise ValueError("d_info must be a CUDA tensor of 8*nframes 4-byte elements")
-    inp = iq_input(d_iq, d_tw, sym_stride, frame_stride, d_start, d_nco, nco_bits, None, nsamples)
+    inp = iq_input(d_iq, d_tw, sym_stride, frame_stride, d_start, d_nco, nco_bits, None, nsamples, iq_format)
     par = SyncParams(int(nfft), int(nsyms), int(nsyms) - 1 if cp_symbols is None else int(cp_symbols), int(W), int(M),
                      float(thr), int(backoff), int(first_start))
+    if iq_format != IQ_F32:
+        fmt = IqFormat(int(iq_format), float(iq_scale))
+        _check(lib().vit_ofdm_sync_iq_dev(C.byref(inp), C.byref(fmt), C.byref(par), _ptr(d_prs), nframes, _ptr(d_start_out),
+                                          _ptr(d_rot_out), _ptr(d_info), _stream_ptr(stream)), "vit_ofdm_sync_iq_dev")
+        return
     _check(lib().vit_ofdm_sync_dev(C.byref(inp), C.byref(par), _ptr(d_prs), nframes, _ptr(d_start_out), _ptr(d_rot_out),
                                    _ptr(d_info), _stream_ptr(stream)), "vit_ofdm_sync_dev")
 

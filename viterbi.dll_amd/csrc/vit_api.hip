@@ -1360,13 +1360,41 @@ int64_t vit_nco_table(uint32_t nco_bits, float* h_nco) {
     return n;
 }
 
+// the rules of vit_iq_format: the float32 format of the existing calls ignores the scale
+static const vit_iq_format IQ_FORMAT_F32 = {VIT_IQ_F32, 1.0f};
+static int iq_check_format(const char* who, const vit_iq_format* fmt) {
+    if (!fmt) {
+        set_err("%s: bad arguments (NULL fmt)", who);
+        return VIT_ERR_ARG;
+    }
+    if (fmt->format > VIT_IQ_CS16) {
+        set_err("%s: bad arguments (format %u, one of VIT_IQ_F32 ... VIT_IQ_CS16)", who, fmt->format);
+        return VIT_ERR_ARG;
+    }
+    if (fmt->format != VIT_IQ_F32 && !(fmt->scale >= 0x1p-32f && fmt->scale <= 0x1p16f)) {  // false for NaN
+        set_err("%s: bad arguments (scale %g, 2^-32 <= scale <= 2^16)", who, (double)fmt->scale);
+        return VIT_ERR_ARG;
+    }
+    return VIT_OK;
+}
+// d_iq: 8-byte aligned float32 pairs, 4-byte aligned integer samples
+static int iq_check_alignment(const char* who, const void* d_iq, const vit_iq_format* fmt) {
+    if (((uintptr_t)d_iq & (fmt->format == VIT_IQ_F32 ? 7u : 3u)) != 0) {
+        set_err("%s: bad arguments (d_iq must be 8-byte aligned, 4-byte aligned for an integer format)", who);
+        return VIT_ERR_ARG;
+    }
+    return VIT_OK;
+}
+
 // the rules of vit_iq_input for frames of nsyms symbols of nfft samples (nfft already checked)
-static int ofdm_check_input(const char* who, const vit_iq_input* in, uint32_t nfft, uint32_t nsyms, int64_t nframes) {
+static int ofdm_check_input(const char* who, const vit_iq_input* in, const vit_iq_format* fmt, uint32_t nfft, uint32_t nsyms,
+                            int64_t nframes) {
     if (!in || !in->d_iq || !in->d_tw || nframes < 0) {
         set_err("%s: bad arguments (NULL in, d_iq or d_tw, or nframes=%lld < 0)", who, (long long)nframes);
         return VIT_ERR_ARG;
     }
-    if (((uintptr_t)in->d_iq & 7u) != 0 || ((uintptr_t)in->d_tw & 7u) != 0 || ((uintptr_t)in->d_nco & 7u) != 0 ||
+    if (iq_check_alignment(who, in->d_iq, fmt) != VIT_OK) return VIT_ERR_ARG;
+    if (((uintptr_t)in->d_tw & 7u) != 0 || ((uintptr_t)in->d_nco & 7u) != 0 ||
         ((uintptr_t)in->d_start & 7u) != 0 || ((uintptr_t)in->d_rot & 7u) != 0) {
         set_err("%s: bad arguments (d_iq, d_tw, d_nco, d_start and d_rot must be 8-byte aligned)", who);
         return VIT_ERR_ARG;
@@ -1393,10 +1421,10 @@ static int ofdm_check_input(const char* who, const vit_iq_input* in, uint32_t nf
     return VIT_OK;
 }
 
-int vit_ofdm_fft_dev(const vit_iq_input* in, uint32_t nfft, uint32_t nsyms, int64_t nframes, float* d_fft,
-                     uint64_t out_sym_stride, uint64_t out_frame_stride, void* stream) {
-    const char* who = "vit_ofdm_fft_dev";
+static int ofdm_fft(const char* who, const vit_iq_input* in, const vit_iq_format* fmt, uint32_t nfft, uint32_t nsyms,
+                    int64_t nframes, float* d_fft, uint64_t out_sym_stride, uint64_t out_frame_stride, void* stream) {
     if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (iq_check_format(who, fmt) != VIT_OK) return VIT_ERR_ARG;
     if (nfft < 64u || nfft > 8192u || (nfft & (nfft - 1u)) != 0 || nsyms == 0) {
         set_err("%s: bad arguments (nfft=%u, a power of two 64 ... 8192; nsyms=%u > 0)", who, nfft, nsyms);
         return VIT_ERR_ARG;
@@ -1407,40 +1435,63 @@ int vit_ofdm_fft_dev(const vit_iq_input* in, uint32_t nfft, uint32_t nsyms, int6
                 "even, out_sym_stride >= nfft)", who, (unsigned long long)out_sym_stride, (unsigned long long)out_frame_stride);
         return VIT_ERR_ARG;
     }
-    if (ofdm_check_input(who, in, nfft, nsyms, nframes) != VIT_OK) return VIT_ERR_ARG;
+    if (ofdm_check_input(who, in, fmt, nfft, nsyms, nframes) != VIT_OK) return VIT_ERR_ARG;
     if (nframes == 0) return VIT_OK;
-    hipError_t e = vit_launch_ofdm_fft(*in, nfft, nsyms, nframes, d_fft, out_sym_stride, out_frame_stride, (hipStream_t)stream);
+    hipError_t e = vit_launch_ofdm_fft(*in, *fmt, nfft, nsyms, nframes, d_fft, out_sym_stride, out_frame_stride, (hipStream_t)stream);
     if (e != hipSuccess) { set_err("OFDM FFT launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
     return VIT_OK;
 }
 
-int vit_ofdm_demod_dev(const vit_iq_input* in, const uint16_t* d_bins, const vit_ofdm_shape* shape, float gain, int64_t nframes,
-                       uint8_t* d_fic, const vit_cif_ring* ring, uint64_t col, void* stream) {
-    const char* who = "vit_ofdm_demod_dev";
+int vit_ofdm_fft_dev(const vit_iq_input* in, uint32_t nfft, uint32_t nsyms, int64_t nframes, float* d_fft,
+                     uint64_t out_sym_stride, uint64_t out_frame_stride, void* stream) {
+    return ofdm_fft("vit_ofdm_fft_dev", in, &IQ_FORMAT_F32, nfft, nsyms, nframes, d_fft, out_sym_stride, out_frame_stride, stream);
+}
+
+int vit_ofdm_fft_iq_dev(const vit_iq_input* in, const vit_iq_format* fmt, uint32_t nfft, uint32_t nsyms, int64_t nframes,
+                        float* d_fft, uint64_t out_sym_stride, uint64_t out_frame_stride, void* stream) {
+    return ofdm_fft("vit_ofdm_fft_iq_dev", in, fmt, nfft, nsyms, nframes, d_fft, out_sym_stride, out_frame_stride, stream);
+}
+
+static int ofdm_demod(const char* who, const vit_iq_input* in, const vit_iq_format* fmt, const uint16_t* d_bins,
+                      const vit_ofdm_shape* shape, float gain, int64_t nframes, uint8_t* d_fic, const vit_cif_ring* ring,
+                      uint64_t col, void* stream) {
     if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (iq_check_format(who, fmt) != VIT_OK) return VIT_ERR_ARG;
     if (!d_bins || !shape || nframes < 0) {
         set_err("%s: bad arguments (NULL d_bins or shape, or nframes=%lld < 0)", who, (long long)nframes);
         return VIT_ERR_ARG;
     }
     if (ofdm_check_outputs(who, shape, gain, nframes, d_fic, ring, col) != VIT_OK) return VIT_ERR_ARG;
-    if (ofdm_check_input(who, in, shape->nfft, shape->nsyms, nframes) != VIT_OK) return VIT_ERR_ARG;
+    if (ofdm_check_input(who, in, fmt, shape->nfft, shape->nsyms, nframes) != VIT_OK) return VIT_ERR_ARG;
     if (nframes == 0) return VIT_OK;
-    hipError_t e = vit_launch_ofdm_demod(*in, d_bins, *shape, gain, nframes, d_fic, ring, col, (hipStream_t)stream);
+    hipError_t e = vit_launch_ofdm_demod(*in, *fmt, d_bins, *shape, gain, nframes, d_fic, ring, col, (hipStream_t)stream);
     if (e != hipSuccess) { set_err("OFDM demodulation launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
     return VIT_OK;
 }
 
+int vit_ofdm_demod_dev(const vit_iq_input* in, const uint16_t* d_bins, const vit_ofdm_shape* shape, float gain, int64_t nframes,
+                       uint8_t* d_fic, const vit_cif_ring* ring, uint64_t col, void* stream) {
+    return ofdm_demod("vit_ofdm_demod_dev", in, &IQ_FORMAT_F32, d_bins, shape, gain, nframes, d_fic, ring, col, stream);
+}
+
+int vit_ofdm_demod_iq_dev(const vit_iq_input* in, const vit_iq_format* fmt, const uint16_t* d_bins, const vit_ofdm_shape* shape,
+                          float gain, int64_t nframes, uint8_t* d_fic, const vit_cif_ring* ring, uint64_t col, void* stream) {
+    return ofdm_demod("vit_ofdm_demod_iq_dev", in, fmt, d_bins, shape, gain, nframes, d_fic, ring, col, stream);
+}
+
 // ---- from the coarse start: fine time and frequency (vit_ofdm_sync.hip) ----------------------------------------------------
-int vit_ofdm_sync_dev(const vit_iq_input* in, const vit_sync_params* p, const float* d_prs, int64_t nframes,
-                      int64_t* d_start_out, uint32_t* d_rot_out, uint32_t* d_info, void* stream) {
-    const char* who = "vit_ofdm_sync_dev";
+static int ofdm_sync(const char* who, const vit_iq_input* in, const vit_iq_format* fmt, const vit_sync_params* p,
+                     const float* d_prs, int64_t nframes, int64_t* d_start_out, uint32_t* d_rot_out, uint32_t* d_info,
+                     void* stream) {
     if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (iq_check_format(who, fmt) != VIT_OK) return VIT_ERR_ARG;
     if (!in || !p || !d_prs || !d_start_out || !d_rot_out || !in->d_iq || !in->d_tw || !in->d_nco || nframes < 0) {
         set_err("%s: bad arguments (NULL in, p, d_iq, d_tw, d_nco, d_prs, d_start_out or d_rot_out, or nframes=%lld < 0)", who,
                 (long long)nframes);
         return VIT_ERR_ARG;
     }
-    if (((uintptr_t)in->d_iq & 7u) != 0 || ((uintptr_t)in->d_tw & 7u) != 0 || ((uintptr_t)in->d_nco & 7u) != 0 ||
+    if (iq_check_alignment(who, in->d_iq, fmt) != VIT_OK) return VIT_ERR_ARG;
+    if (((uintptr_t)in->d_tw & 7u) != 0 || ((uintptr_t)in->d_nco & 7u) != 0 ||
         ((uintptr_t)in->d_start & 7u) != 0 || ((uintptr_t)d_prs & 7u) != 0 || ((uintptr_t)d_start_out & 7u) != 0 ||
         ((uintptr_t)d_rot_out & 7u) != 0 || ((uintptr_t)d_info & 3u) != 0) {
         set_err("%s: bad arguments (d_iq, d_tw, d_nco, d_start, d_prs, d_start_out and d_rot_out must be 8-byte aligned, d_info "
@@ -1482,8 +1533,38 @@ int vit_ofdm_sync_dev(const vit_iq_input* in, const vit_sync_params* p, const fl
         }
     }
     if (nframes == 0) return VIT_OK;
-    hipError_t e = vit_launch_ofdm_sync(*in, *p, d_prs, nframes, d_start_out, d_rot_out, d_info, (hipStream_t)stream);
+    hipError_t e = vit_launch_ofdm_sync(*in, *fmt, *p, d_prs, nframes, d_start_out, d_rot_out, d_info, (hipStream_t)stream);
     if (e != hipSuccess) { set_err("OFDM synchronisation launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
+    return VIT_OK;
+}
+
+int vit_ofdm_sync_dev(const vit_iq_input* in, const vit_sync_params* p, const float* d_prs, int64_t nframes,
+                      int64_t* d_start_out, uint32_t* d_rot_out, uint32_t* d_info, void* stream) {
+    return ofdm_sync("vit_ofdm_sync_dev", in, &IQ_FORMAT_F32, p, d_prs, nframes, d_start_out, d_rot_out, d_info, stream);
+}
+
+int vit_ofdm_sync_iq_dev(const vit_iq_input* in, const vit_iq_format* fmt, const vit_sync_params* p, const float* d_prs,
+                         int64_t nframes, int64_t* d_start_out, uint32_t* d_rot_out, uint32_t* d_info, void* stream) {
+    return ofdm_sync("vit_ofdm_sync_iq_dev", in, fmt, p, d_prs, nframes, d_start_out, d_rot_out, d_info, stream);
+}
+
+// ---- integer samples to the floats of the definition (vit_iq_convert.hip) ----------------------------------------------
+int vit_iq_convert_dev(const void* d_iq, const vit_iq_format* fmt, uint64_t nsamples, float* d_out, void* stream) {
+    const char* who = "vit_iq_convert_dev";
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (iq_check_format(who, fmt) != VIT_OK) return VIT_ERR_ARG;
+    if (fmt->format == VIT_IQ_F32) {
+        set_err("%s: bad arguments (format VIT_IQ_F32: nothing to convert)", who);
+        return VIT_ERR_ARG;
+    }
+    if (!d_iq || !d_out || ((uintptr_t)d_iq & 3u) != 0 || ((uintptr_t)d_out & 7u) != 0 || nsamples > (UINT64_MAX >> 4)) {
+        set_err("%s: bad arguments (NULL d_iq or d_out, d_iq not 4-byte or d_out not 8-byte aligned, or nsamples=%llu >= 2^60)",
+                who, (unsigned long long)nsamples);
+        return VIT_ERR_ARG;
+    }
+    if (nsamples == 0) return VIT_OK;
+    hipError_t e = vit_launch_iq_convert(d_iq, *fmt, nsamples, d_out, (hipStream_t)stream);
+    if (e != hipSuccess) { set_err("sample conversion launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
     return VIT_OK;
 }
 

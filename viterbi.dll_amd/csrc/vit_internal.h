@@ -102,13 +102,17 @@ int64_t vit_fft_twiddles_host(uint32_t nfft, float* h_tw);
 int64_t vit_nco_table_host(uint32_t nco_bits, float* h_nco);
 // Rotation and FFT of nframes frames, then the spectra to d_fft (vit_launch_ofdm_fft) or the demapping of
 // vit_launch_ofdm_demap without a spectrum in memory (vit_launch_ofdm_demod); the caller has checked every argument rule.
-hipError_t vit_launch_ofdm_fft(const vit_iq_input& in, uint32_t nfft, uint32_t nsyms, int64_t nframes, float* d_fft,
+// fmt: the samples' format (format and scale checked by the caller; VIT_IQ_F32 ignores the scale).
+hipError_t vit_launch_ofdm_fft(const vit_iq_input& in, const vit_iq_format& fmt, uint32_t nfft, uint32_t nsyms, int64_t nframes, float* d_fft,
                                uint64_t out_sym_stride, uint64_t out_frame_stride, hipStream_t stream);
-hipError_t vit_launch_ofdm_demod(const vit_iq_input& in, const uint16_t* d_bins, const vit_ofdm_shape& shape, float gain,
+hipError_t vit_launch_ofdm_demod(const vit_iq_input& in, const vit_iq_format& fmt, const uint16_t* d_bins, const vit_ofdm_shape& shape, float gain,
                                  int64_t nframes, uint8_t* d_fic, const vit_cif_ring* ring, uint64_t col, hipStream_t stream);
 // From the coarse start (vit_ofdm_sync.hip): one workgroup per frame; the caller has checked every argument rule.
-hipError_t vit_launch_ofdm_sync(const vit_iq_input& in, const vit_sync_params& p, const float* d_prs, int64_t nframes,
+hipError_t vit_launch_ofdm_sync(const vit_iq_input& in, const vit_iq_format& fmt, const vit_sync_params& p, const float* d_prs, int64_t nframes,
                                 int64_t* d_start_out, uint32_t* d_rot_out, uint32_t* d_info, hipStream_t stream);
+// Integer samples to the floats of the definition (vit_iq_convert.hip): 2*nsamples floats to d_out; fmt is an integer
+// format, checked by the caller like the alignments.
+hipError_t vit_launch_iq_convert(const void* d_iq, const vit_iq_format& fmt, uint64_t nsamples, float* d_out, hipStream_t stream);
 // After the decoder (vit_dab.hip).  The energy dispersal PRBS of one frame, (framebits+7)/8 bytes, padding bits 0
 // (framebits even, <= 9216; the caller checks).
 int64_t vit_prbs_bytes_host(uint8_t* h_out, uint32_t framebits);

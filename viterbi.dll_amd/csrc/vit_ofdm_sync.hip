@@ -17,9 +17,12 @@
 //   D  Z[k] = Y[k + m^] conj(P[k]) is read into registers, a barrier, and conj Z is transformed in place of Y; the
 //      powers |h|^2 are reduced from LDS (sum, maximum over 0 ... 2W, first index over the threshold).
 // Thread 0 writes the frame's 1 + 2 + 8 words.
+// Integer sample formats (vit_iq_dev.h): one template flag apart from the float32 instantiations.  Only the loads of A
+// and B change - the pairs in flight stay raw until they are accumulated - and A's loop is written once per format.
 #pragma clang fp contract(off)
 #include "vit_fft_dev.h"
 #include "vit_internal.h"
+#include "vit_iq_dev.h"
 
 namespace {
 
@@ -46,6 +49,9 @@ struct SyncArgs {
     long long* start_out;
     uint2* rot_out;
     u32* info;
+    // integer sample formats: iq then points at samples of iq_fmt (VIT_IQ_CU8 ... VIT_IQ_CS16)
+    u32 iq_fmt;
+    float iq_scale;
 };
 
 // LDS behind the symbol and the twiddles, in floats; J wavefronts
@@ -98,7 +104,48 @@ __device__ __forceinline__ float turn_of(float re, float im) {
     return r;
 }
 
-template <u32 M_>
+// step A on an integer format FMT: the loop of the float32 kernel with the pairs in flight kept raw
+template <u32 FMT, u32 N, u32 TPB>
+__device__ __forceinline__ void guard_sums_int(const SyncArgs& A, long long c, u32 T, float& gr, float& gi, float& en) {
+    constexpr u32 SB = vit_iq::sample_bytes(FMT);
+    const u32 Gw = A.G - 2u * A.W;
+    const u64 total = (u64)A.cp * Gw;
+    const char* guard0 = reinterpret_cast<const char*>(A.iq) + (c + N + A.W) * (long long)SB;
+    const u32 dq = TPB / Gw, dr = TPB % Gw;
+    u32 l = T / Gw, k = T % Gw;
+    for (u64 e = T; e < total; e += (u64)PAIRS_IN_FLIGHT * TPB) {
+        u32 ra[PAIRS_IN_FLIGHT], rb[PAIRS_IN_FLIGHT];
+#pragma unroll
+        for (u32 u = 0; u < PAIRS_IN_FLIGHT; u++) {
+            ra[u] = rb[u] = 0u;
+            if (e + (u64)u * TPB < total) {
+                const char* p = guard0 + ((u64)l * A.sym_stride + k) * SB;
+                u32 two[2];
+                vit_iq::iq_load_raw<2>(p, FMT, two, [](u32 j) { return j * N; });
+                ra[u] = two[0];
+                rb[u] = two[1];
+            }
+            k += dr;
+            l += dq;
+            if (k >= Gw) {
+                k -= Gw;
+                l++;
+            }
+        }
+        float2 a[PAIRS_IN_FLIGHT], b[PAIRS_IN_FLIGHT];
+        vit_iq::iq_convert<PAIRS_IN_FLIGHT>(ra, FMT, A.iq_scale, a);
+        vit_iq::iq_convert<PAIRS_IN_FLIGHT>(rb, FMT, A.iq_scale, b);
+#pragma unroll
+        for (u32 u = 0; u < PAIRS_IN_FLIGHT; u++)
+            if (e + (u64)u * TPB < total) {
+                gr = gr + (a[u].x * b[u].x + a[u].y * b[u].y);
+                gi = gi + (a[u].x * b[u].y - a[u].y * b[u].x);
+                en = en + ((a[u].x * a[u].x + a[u].y * a[u].y) + (b[u].x * b[u].x + b[u].y * b[u].y));
+            }
+    }
+}
+
+template <u32 M_, bool INT>
 __global__ __launch_bounds__(Cfg<M_>::TPB) void vit_ofdm_sync_kernel(SyncArgs A) {
     typedef Cfg<M_> C;
     constexpr u32 N = C::N, TA = C::TA, TPB = C::TPB, J = TPB / 64u, KPT = N / TPB;
@@ -136,7 +183,12 @@ __global__ __launch_bounds__(Cfg<M_>::TPB) void vit_ofdm_sync_kernel(SyncArgs A)
     const u32 dq = TPB / Gw, dr = TPB % Gw;
     u32 l = T / Gw, k = T % Gw;
     float gr = 0.f, gi = 0.f, en = 0.f;
-    for (u64 e = T; e < total; e += (u64)PAIRS_IN_FLIGHT * TPB) {
+    if constexpr (INT) {
+        if (A.iq_fmt == VIT_IQ_CU8) guard_sums_int<VIT_IQ_CU8, N, TPB>(A, c, T, gr, gi, en);
+        else if (A.iq_fmt == VIT_IQ_CS8) guard_sums_int<VIT_IQ_CS8, N, TPB>(A, c, T, gr, gi, en);
+        else guard_sums_int<VIT_IQ_CS16, N, TPB>(A, c, T, gr, gi, en);
+    }
+    for (u64 e = T; !INT && e < total; e += (u64)PAIRS_IN_FLIGHT * TPB) {
         float2 a[PAIRS_IN_FLIGHT], b[PAIRS_IN_FLIGHT];
 #pragma unroll
         for (u32 u = 0; u < PAIRS_IN_FLIGHT; u++) {
@@ -180,11 +232,18 @@ __global__ __launch_bounds__(Cfg<M_>::TPB) void vit_ofdm_sync_kernel(SyncArgs A)
     // ---- B: the phase reference symbol's window at c - W, rotated by step_frac, transformed
     if (active) {
         const float2* win = A.iq + (c - (long long)A.W);
+        float2 xi[INT ? 8 : 1];
+        if constexpr (INT) {
+            u32 raw[8];
+            const char* wi = reinterpret_cast<const char*>(A.iq) + (c - (long long)A.W) * (long long)vit_iq::sample_bytes(A.iq_fmt);
+            vit_iq::iq_load_raw<8>(wi, A.iq_fmt, raw, [T](u32 j) { return input_index<M_>(T, j); });
+            vit_iq::iq_convert<8>(raw, A.iq_fmt, A.iq_scale, xi);
+        }
         float2 x[8];
 #pragma unroll
         for (u32 j = 0; j < 8; j++) {
             const u32 i = input_index<M_>(T, j);
-            const float2 v = win[i];
+            const float2 v = INT ? xi[INT ? j : 0] : win[i];
             const float2 w = A.nco[(i * step_frac) >> A.nco_shift];
             x[j] = make_float2(v.x * w.x - v.y * w.y, v.x * w.y + v.y * w.x);
         }
@@ -324,25 +383,30 @@ __global__ __launch_bounds__(Cfg<M_>::TPB) void vit_ofdm_sync_kernel(SyncArgs A)
     }
 }
 
-template <u32 M_>
-hipError_t launch_sync(const SyncArgs& A, int64_t nframes, hipStream_t stream) {
+template <u32 M_, bool INT>
+hipError_t launch_sync2(const SyncArgs& A, int64_t nframes, hipStream_t stream) {
     typedef Cfg<M_> C;
     const size_t lds = C::LDS_BYTES + Scratch<C::TPB / 64u>::FLOATS * 4u;
     if (lds > 64u * 1024u) {
         static uint64_t optin_done = 0;
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        const void* ks[1] = {reinterpret_cast<const void*>(&vit_ofdm_sync_kernel<M_>)};
+        const void* ks[1] = {reinterpret_cast<const void*>(&vit_ofdm_sync_kernel<M_, INT>)};
         const hipError_t e = vit_optin_dynamic_lds(ks, 1, 160 * 1024, dev, &optin_done);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((vit_ofdm_sync_kernel<M_>), dim3((unsigned)nframes), dim3(C::TPB), lds, stream, A);
+    hipLaunchKernelGGL((vit_ofdm_sync_kernel<M_, INT>), dim3((unsigned)nframes), dim3(C::TPB), lds, stream, A);
     return hipGetLastError();
+}
+
+template <u32 M_>
+hipError_t launch_sync(const SyncArgs& A, int64_t nframes, hipStream_t stream) {
+    return A.iq_fmt == VIT_IQ_F32 ? launch_sync2<M_, false>(A, nframes, stream) : launch_sync2<M_, true>(A, nframes, stream);
 }
 
 }  // namespace
 
-hipError_t vit_launch_ofdm_sync(const vit_iq_input& in, const vit_sync_params& p, const float* d_prs, int64_t nframes,
+hipError_t vit_launch_ofdm_sync(const vit_iq_input& in, const vit_iq_format& fmt, const vit_sync_params& p, const float* d_prs, int64_t nframes,
                                 int64_t* d_start_out, uint32_t* d_rot_out, uint32_t* d_info, hipStream_t stream) {
     if (nframes <= 0) return hipSuccess;
     if (nframes > 0x7FFFFFFFll) return hipErrorInvalidValue;
@@ -367,6 +431,8 @@ hipError_t vit_launch_ofdm_sync(const vit_iq_input& in, const vit_sync_params& p
     A.start_out = reinterpret_cast<long long*>(d_start_out);
     A.rot_out = reinterpret_cast<uint2*>(d_rot_out);
     A.info = d_info;
+    A.iq_fmt = fmt.format;
+    A.iq_scale = fmt.scale;
     switch (p.nfft) {
         case 64: return launch_sync<6>(A, nframes, stream);
         case 128: return launch_sync<7>(A, nframes, stream);

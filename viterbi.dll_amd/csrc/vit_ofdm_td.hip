@@ -19,12 +19,16 @@
 // Demapping: carrier n reads bin d_bins[n] of the LDS spectrum; a thread owns fixed groups of 4 consecutive n, keeps
 // their bins and the previous symbol's values in registers and stores 4 + 4 soft bytes per group (any alignment).  A run
 // starts by transforming the symbol before it: 1/run of redundant work.
+// Integer sample formats (vit_iq_dev.h): one template flag apart from the float32 instantiations, which stay what they
+// were.  The prefetched samples are then kept raw, 8 dwords instead of 16, and converted where the first pass consumes
+// them; the three formats share an instantiation and part in two scalar branches of the loader.
 #pragma clang fp contract(off)
 #include <cfloat>
 #include <cmath>
 
 #include "vit_fft_dev.h"
 #include "vit_internal.h"
+#include "vit_iq_dev.h"
 
 namespace {
 
@@ -51,6 +55,9 @@ struct TdArgs {
     uint8_t* fic;
     uint8_t* ring;
     u64 row_bytes, nrows, first_row, col;
+    // integer sample formats: iq then points at samples of iq_fmt (VIT_IQ_CU8 ... VIT_IQ_CS16)
+    u32 iq_fmt;
+    float iq_scale;
 };
 
 
@@ -69,20 +76,30 @@ __device__ __forceinline__ u32 soft_pair(float ar, float ai, float br, float bi,
     return q;
 }
 
-template <u32 M, bool ROT>
+template <u32 M, bool ROT, bool INT>
 struct Samples {
-    float2 x[8];
+    float2 x[INT ? 1 : 8];
+    u32 raw[INT ? 8 : 1];  // integer formats: as they lie in memory, converted by the first pass
     float2 w[ROT ? 8 : 1];
 };
 
 // symbol l's samples of thread T: group k of the first pass is T + k*TA, its point c is sample gid + c*N/R
-template <u32 M, bool ROT>
-__device__ __forceinline__ void load_samples(const TdArgs& A, const float2* frame, u32 l, u32 ph0, u32 step, u32 T,
-                                             Samples<M, ROT>& s) {
+template <u32 M, bool ROT, bool INT>
+__device__ __forceinline__ void load_samples(const TdArgs& A, const void* frame, u32 l, u32 ph0, u32 step, u32 T,
+                                             Samples<M, ROT, INT>& s) {
     typedef Cfg<M> C;
     constexpr u32 R = 1u << C::R1, NG = C::N / R;
-    const float2* sym = frame + (u64)l * A.sym_stride;
     const u32 n0 = (u32)((u64)l * A.sym_stride);  // mod 2^32, like the phase
+    if constexpr (INT) {
+        const char* sym = static_cast<const char*>(frame) + (u64)l * A.sym_stride * vit_iq::sample_bytes(A.iq_fmt);
+        vit_iq::iq_load_raw<8>(sym, A.iq_fmt, s.raw, [T](u32 j) { return input_index<M>(T, j); });
+        if (ROT) {
+#pragma unroll
+            for (u32 j = 0; j < 8; j++) s.w[j] = A.nco[(ph0 + (n0 + input_index<M>(T, j)) * step) >> A.nco_shift];
+        }
+        return;
+    }
+    const float2* sym = static_cast<const float2*>(frame) + (u64)l * A.sym_stride;
 #pragma unroll
     for (u32 k = 0; k < 8u / R; k++)
 #pragma unroll
@@ -93,7 +110,7 @@ __device__ __forceinline__ void load_samples(const TdArgs& A, const float2* fram
         }
 }
 
-template <u32 M, bool ROT, bool DEMAP>
+template <u32 M, bool ROT, bool DEMAP, bool INT>
 __global__ __launch_bounds__(Cfg<M>::TPB) __attribute__((amdgpu_waves_per_eu(Cfg<M>::waves(ROT), Cfg<M>::waves(ROT)))) void vit_ofdm_td_kernel(TdArgs A) {
     typedef Cfg<M> C;
     constexpr u32 N = C::N, TA = C::TA, R1 = C::R1, R = 1u << R1, NP = C::NP;
@@ -106,7 +123,8 @@ __global__ __launch_bounds__(Cfg<M>::TPB) __attribute__((amdgpu_waves_per_eu(Cfg
         st = A.start[t];
         if (st < 0 || (u64)st > A.nsamples || A.extent > A.nsamples - (u64)st) return;
     }
-    const float2* frame = A.iq + st;
+    const void* frame = INT ? static_cast<const void*>(reinterpret_cast<const char*>(A.iq) + st * (long long)vit_iq::sample_bytes(A.iq_fmt))
+                            : static_cast<const void*>(A.iq + st);
     const u32 s0 = A.lo + (u32)(blockIdx.x % A.runs) * A.run, s1 = s0 + A.run < A.hi ? s0 + A.run : A.hi;
     const u32 l1 = DEMAP ? s1 : s1 - 1u;  // the symbols s0 ... l1 are transformed
     u32 ph0 = 0, step = 0;
@@ -141,16 +159,18 @@ __global__ __launch_bounds__(Cfg<M>::TPB) __attribute__((amdgpu_waves_per_eu(Cfg
             }
     }
 
-    Samples<M, ROT> smp;
-    if (active) load_samples<M, ROT>(A, frame, s0, ph0, step, T, smp);
+    Samples<M, ROT, INT> smp;
+    if (active) load_samples<M, ROT, INT>(A, frame, s0, ph0, step, T, smp);
     for (u32 l = s0; l <= l1; l++) {
         if (active) {
+            float2 xi[INT ? 8 : 1];
+            if constexpr (INT) vit_iq::iq_convert<8>(smp.raw, A.iq_fmt, A.iq_scale, xi);
 #pragma unroll
             for (u32 k = 0; k < 8u / R; k++) {
                 float2 v[R];
 #pragma unroll
                 for (u32 c = 0; c < R; c++) {
-                    float2 x = smp.x[k * R + c];
+                    float2 x = INT ? xi[INT ? k * R + c : 0] : smp.x[INT ? 0 : k * R + c];
                     if (ROT) {
                         const float2 ww = smp.w[k * R + c];
                         x = make_float2(x.x * ww.x - x.y * ww.y, x.x * ww.y + x.y * ww.x);
@@ -162,7 +182,7 @@ __global__ __launch_bounds__(Cfg<M>::TPB) __attribute__((amdgpu_waves_per_eu(Cfg
 #pragma unroll
                 for (u32 q = 0; q < R; q++) g[q] = v[q];
             }
-            if (l < l1) load_samples<M, ROT>(A, frame, l + 1u, ph0, step, T, smp);
+            if (l < l1) load_samples<M, ROT, INT>(A, frame, l + 1u, ph0, step, T, smp);
         }
         __syncthreads();
 #pragma unroll
@@ -227,25 +247,30 @@ __global__ __launch_bounds__(Cfg<M>::TPB) __attribute__((amdgpu_waves_per_eu(Cfg
     }
 }
 
-template <u32 M, bool ROT, bool DEMAP>
+template <u32 M, bool ROT, bool DEMAP, bool INT>
 hipError_t launch3(const TdArgs& A, u64 grid, hipStream_t stream) {
     const size_t lds = Cfg<M>::LDS_BYTES;
     if (lds > 64u * 1024u) {
         static uint64_t optin_done = 0;
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        const void* ks[1] = {reinterpret_cast<const void*>(&vit_ofdm_td_kernel<M, ROT, DEMAP>)};
+        const void* ks[1] = {reinterpret_cast<const void*>(&vit_ofdm_td_kernel<M, ROT, DEMAP, INT>)};
         const hipError_t e = vit_optin_dynamic_lds(ks, 1, 160 * 1024, dev, &optin_done);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((vit_ofdm_td_kernel<M, ROT, DEMAP>), dim3((unsigned)grid), dim3(Cfg<M>::TPB), lds, stream, A);
+    hipLaunchKernelGGL((vit_ofdm_td_kernel<M, ROT, DEMAP, INT>), dim3((unsigned)grid), dim3(Cfg<M>::TPB), lds, stream, A);
     return hipGetLastError();
+}
+
+template <u32 M, bool INT>
+hipError_t launch2i(const TdArgs& A, bool demap, u64 grid, hipStream_t stream) {
+    if (A.rot) return demap ? launch3<M, true, true, INT>(A, grid, stream) : launch3<M, true, false, INT>(A, grid, stream);
+    return demap ? launch3<M, false, true, INT>(A, grid, stream) : launch3<M, false, false, INT>(A, grid, stream);
 }
 
 template <u32 M>
 hipError_t launch2(const TdArgs& A, bool demap, u64 grid, hipStream_t stream) {
-    if (A.rot) return demap ? launch3<M, true, true>(A, grid, stream) : launch3<M, true, false>(A, grid, stream);
-    return demap ? launch3<M, false, true>(A, grid, stream) : launch3<M, false, false>(A, grid, stream);
+    return A.iq_fmt == VIT_IQ_F32 ? launch2i<M, false>(A, demap, grid, stream) : launch2i<M, true>(A, demap, grid, stream);
 }
 
 // workgroups of the TdArgs' symbol range: about 8 per CU over the whole grid, RUN_MAX symbols per run at most
@@ -276,9 +301,11 @@ hipError_t launch(TdArgs& A, u32 nfft, bool demap, int64_t nframes, hipStream_t 
     return hipErrorInvalidValue;
 }
 
-TdArgs input_args(const vit_iq_input& in, u32 nfft, u32 nsyms) {
+TdArgs input_args(const vit_iq_input& in, const vit_iq_format& fmt, u32 nfft, u32 nsyms) {
     TdArgs A = {};
     A.iq = reinterpret_cast<const float2*>(in.d_iq);
+    A.iq_fmt = fmt.format;
+    A.iq_scale = fmt.scale;
     A.nsamples = in.nsamples;
     A.sym_stride = in.sym_stride;
     A.frame_stride = in.frame_stride;
@@ -324,9 +351,9 @@ int64_t vit_nco_table_host(uint32_t nco_bits, float* h_nco) {
     return (int64_t)n;
 }
 
-hipError_t vit_launch_ofdm_fft(const vit_iq_input& in, uint32_t nfft, uint32_t nsyms, int64_t nframes, float* d_fft,
+hipError_t vit_launch_ofdm_fft(const vit_iq_input& in, const vit_iq_format& fmt, uint32_t nfft, uint32_t nsyms, int64_t nframes, float* d_fft,
                                uint64_t out_sym_stride, uint64_t out_frame_stride, hipStream_t stream) {
-    TdArgs A = input_args(in, nfft, nsyms);
+    TdArgs A = input_args(in, fmt, nfft, nsyms);
     A.lo = 0;
     A.hi = nsyms;
     A.out = reinterpret_cast<float2*>(d_fft);
@@ -335,9 +362,9 @@ hipError_t vit_launch_ofdm_fft(const vit_iq_input& in, uint32_t nfft, uint32_t n
     return launch(A, nfft, false, nframes, stream);
 }
 
-hipError_t vit_launch_ofdm_demod(const vit_iq_input& in, const uint16_t* d_bins, const vit_ofdm_shape& shape, float gain,
+hipError_t vit_launch_ofdm_demod(const vit_iq_input& in, const vit_iq_format& fmt, const uint16_t* d_bins, const vit_ofdm_shape& shape, float gain,
                                  int64_t nframes, uint8_t* d_fic, const vit_cif_ring* ring, uint64_t col, hipStream_t stream) {
-    TdArgs A = input_args(in, shape.nfft, shape.nsyms);
+    TdArgs A = input_args(in, fmt, shape.nfft, shape.nsyms);
     A.bins = d_bins;
     A.K = shape.ncarriers;
     A.fic_syms = shape.fic_syms;
