@@ -430,7 +430,8 @@ int vit_ofdm_demap_dev(const float *d_fft, uint64_t sym_stride, uint64_t frame_s
  * between useful parts, not the null symbol.  Any sample position is allowed; only d_iq must be 8-byte aligned.
  * The two tables come from vit_ofdm_sync_dev ("From the coarse start", below) or from the caller's own estimator.
  * Integer samples as receivers deliver them go through the *_iq_dev calls ("Integer sample formats", below).
- * Out of scope: first acquisition (finding the null symbol), resampling, channel-state weighting. */
+ * Channel-state weighting is a second soft-decision rule of both demappers ("Channel-state weighting", below).
+ * Out of scope: first acquisition (finding the null symbol), resampling. */
 typedef struct vit_iq_input {
     const float    *d_iq;         /* interleaved (re, im) float32 samples, 8-byte aligned (*_iq_dev: samples of fmt->format) */
     uint64_t        nsamples;     /* complex samples in d_iq: nothing at or beyond it is read */
@@ -612,6 +613,62 @@ int vit_ofdm_demod_iq_dev(const vit_iq_input *in, const vit_iq_format *fmt, cons
 int vit_ofdm_sync_iq_dev(const vit_iq_input *in, const vit_iq_format *fmt, const vit_sync_params *p, const float *d_prs,
                          int64_t nframes, int64_t *d_start_out, uint32_t *d_rot_out, uint32_t *d_info, void *stream);
 int vit_iq_convert_dev(const void *d_iq, const vit_iq_format *fmt, uint64_t nsamples, float *d_out, void *stream);
+
+/* Channel-state weighting: a second soft-decision rule.  The definition of vit_ofdm_demap_dev scales every carrier by its
+ * own |re| + |im|, so a carrier in a fading notch reaches the decoder with the confidence of the strongest one.  The
+ * per-symbol rule scales all K carriers of an OFDM symbol by one value, taken from the mean of |re| + |im| over the
+ * symbol: a carrier's soft value then grows with its strength (|H|^2 for differential detection), which is the weight a
+ * Viterbi decoder wants.  The existing calls, their bytes and their kernels are untouched; the rule is a HOST struct read
+ * during the call. */
+#define VIT_SOFT_PER_CARRIER 0   /* the definition of vit_ofdm_demap_dev */
+#define VIT_SOFT_PER_SYMBOL  1
+typedef struct vit_soft_rule {
+    uint32_t rule;        /* VIT_SOFT_* */
+    float    gain;        /* PER_CARRIER: 0 < gain <= 65536;  PER_SYMBOL: 2^-24 <= gain <= 65536 */
+} vit_soft_rule;
+/* Definition of VIT_SOFT_PER_SYMBOL.  Every operation is one IEEE binary32 operation, rounded to nearest-even, in exactly
+ * this order, never contracted into an FMA.  Per data symbol:
+ * 1. re, im and nrm of every n = 0 ... K-1 exactly as in vit_ofdm_demap_dev.
+ *      v[n] = nrm[n]  if 2^-64 <= nrm[n] <= FLT_MAX,  else +0          (no signal, NaN, Inf: the carrier is an erasure)
+ * 2. The symbol's level S = the sum of v in a grouping that depends on nfft and K alone - never on nframes, the launch or
+ *    the device - in the shape of the long sums of "From the coarse start":
+ *      groups        q[g] = fl( fl(v[4g] + v[4g+1]) + fl(v[4g+2] + v[4g+3]) )  for g < ceil(K/4); a v[n] with n >= K is +0
+ *      accumulators  A = max(64, nfft/8) of them:  acc[i] = q[i], then acc[i] = fl(acc[i] + q[i+A]), then + q[i+2A] ... in
+ *                    this order while the group exists (K <= nfft: at most two); acc[i] = +0 for i >= ceil(K/4)
+ *      tree          the accumulators meet in the tree of adjacent pairs: u[i] = fl(u[2i] + u[2i+1]) until one is left
+ *    All terms are non-negative: an overflow gives +Inf, never NaN.
+ * 3. If not (2^-64 <= S <= 2^96): all 2K bytes of the symbol are 128 (no signal at all, or a level beyond any receiver's).
+ * 4. Otherwise  s = fl( fl(gain * fl(K)) / S )                          fl(K) is exact
+ *      a carrier with v[n] = +0:  out[n] = out[n+K] = 128
+ *      every other carrier:       out[n]   = clamp(128 - rint(fl(re*s)), 0, 255)
+ *                                 out[n+K] = clamp(128 - rint(fl(im*s)), 0, 255)      rint: ties to even
+ *    An ideal constellation point on a carrier of the symbol's mean strength gives 128 -/+ gain/2; a carrier of twice the
+ *    mean amplitude four times that excursion, up to the clamp.  Gains of 64 ... 128 suit the decoders here (INTEGRATION.md
+ *    2i); the per-carrier rule's 254 would clamp every carrier above the mean.
+ * The bounds, checked: gain*K lies in [2^-24, 2^29] and S in [2^-64, 2^96], so s lies in [2^-120, 2^93] and is a normal
+ * number.  Every term of S is 0 or at least 2^-64, so no partial sum is denormal.  re and im of a carrier that is no
+ * erasure are finite (nrm <= FLT_MAX).  fl(re*s) may be denormal or, with flushing, 0 - then |re*s| < 2^-126 and rint
+ * gives 0 either way; a denormal re times s <= 2^93 stays under 2^-33 and rounds to 0 either way; an overflow of re*s
+ * gives +-Inf and clamps.  So no byte depends on how denormals are handled, as in the per-carrier rule.
+ * No run of symbols influences another symbol: a symbol's bytes and level are the same in every launch.
+ *
+ * The two calls: vit_ofdm_demap_soft_dev is vit_ofdm_demap_dev, and vit_ofdm_demod_soft_dev is vit_ofdm_demod_iq_dev (fmt
+ * NULL: float32 samples, vit_ofdm_demod_dev), with `soft` in the place of gain.  Every argument that soft does not replace
+ * means what it means there: destinations, skipped frames, guarantees and argument rules.  With VIT_SOFT_PER_CARRIER the
+ * call dispatches to the existing kernels and gives the existing call's bytes; d_level must then be NULL.
+ * d_level: optional DEVICE table of nframes * (nsyms-1) floats, 4-byte aligned.  Word t*(nsyms-1) + s receives S of data
+ * symbol s of frame t, for the symbols the call demaps (FIC only, MSC only or both); the other words, and all words of a
+ * frame skipped through d_start, keep their old value.  It is the caller's signal-level and lock input (S / K is the mean
+ * of |re| + |im|, about sqrt 2 times the mean carrier power), and it makes the summation order observable.
+ * In addition VIT_ERR_ARG (with vit_last_error()) for a NULL soft, a rule other than the two, d_level with
+ * VIT_SOFT_PER_CARRIER, a misaligned d_level, and with VIT_SOFT_PER_SYMBOL a gain outside [2^-24, 65536] (NaN included). */
+int vit_ofdm_demap_soft_dev(const float *d_fft, uint64_t sym_stride, uint64_t frame_stride, const uint16_t *d_bins,
+                            const vit_ofdm_shape *shape, const vit_soft_rule *soft, int64_t nframes, uint8_t *d_fic,
+                            const vit_cif_ring *ring, uint64_t col, float *d_level, void *stream);
+int vit_ofdm_demod_soft_dev(const vit_iq_input *in, const vit_iq_format *fmt /* NULL: float32 */,
+                            const uint16_t *d_bins, const vit_ofdm_shape *shape, const vit_soft_rule *soft,
+                            int64_t nframes, uint8_t *d_fic, const vit_cif_ring *ring, uint64_t col,
+                            float *d_level, void *stream);
 
 /* Kernel selection (the analogue of the reference's dispatcher, setupdll.cpp:195-270):
  *   0 = auto: launches of up to 2048 frames (they cannot fill the chip) take the latency kernel - one

@@ -33,6 +33,7 @@ EXPORTS = [
     "vit_freq_interleave_bins", "vit_ofdm_demap_dev",
     "vit_fft_twiddles", "vit_nco_table", "vit_ofdm_fft_dev", "vit_ofdm_demod_dev", "vit_ofdm_sync_dev",
     "vit_ofdm_fft_iq_dev", "vit_ofdm_demod_iq_dev", "vit_ofdm_sync_iq_dev", "vit_iq_convert_dev",
+    "vit_ofdm_demap_soft_dev", "vit_ofdm_demod_soft_dev",
     "vit_decode_stream_multi",
 ]
 MULTI_LOOPBACK = 0x1
@@ -94,6 +95,15 @@ class IqFormat(C.Structure):
 # the sample formats of include/viterbi_amd.h (VIT_IQ_*) and the tensor types that hold them
 IQ_F32, IQ_CU8, IQ_CS8, IQ_CS16 = 0, 1, 2, 3
 _IQ_DTYPES = {IQ_CU8: "torch.uint8", IQ_CS8: "torch.int8", IQ_CS16: "torch.int16"}
+
+
+class SoftRule(C.Structure):
+    """vit_soft_rule of include/viterbi_amd.h: SoftRule(rule, gain)"""
+    _fields_ = [("rule", C.c_uint32), ("gain", C.c_float)]
+
+
+# the soft-decision rules of include/viterbi_amd.h (VIT_SOFT_*)
+SOFT_PER_CARRIER, SOFT_PER_SYMBOL = 0, 1
 
 
 class SyncParams(C.Structure):
@@ -188,6 +198,10 @@ def lib():
         L.vit_ofdm_demod_iq_dev.argtypes = [pi, pf] + L.vit_ofdm_demod_dev.argtypes[1:]
         L.vit_ofdm_sync_iq_dev.argtypes = [pi, pf] + L.vit_ofdm_sync_dev.argtypes[1:]
         L.vit_iq_convert_dev.argtypes = [vp, pf, C.c_uint64, vp, vp]
+        ps = C.POINTER(SoftRule)
+        L.vit_ofdm_demap_soft_dev.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.POINTER(OfdmShape), ps, C.c_int64, vp, pr,
+                                              C.c_uint64, vp, vp]
+        L.vit_ofdm_demod_soft_dev.argtypes = [pi, pf, vp, C.POINTER(OfdmShape), ps, C.c_int64, vp, pr, C.c_uint64, vp, vp]
         _lib = L
     return _lib
 
@@ -683,6 +697,60 @@ def ofdm_demod_dev(d_iq, shape, d_bins, gain, nframes, d_tw, sym_stride, frame_s
         return
     _check(lib().vit_ofdm_demod_dev(C.byref(inp), _ptr(d_bins), C.byref(shape), float(gain), nframes, _ptr(d_fic), ring, col,
                                     _stream_ptr(stream)), "vit_ofdm_demod_dev")
+
+
+def _soft_rule(rule, gain, d_level, shape, nframes):
+    """SoftRule of the *_soft_dev wrappers; ValueError for a rule that is none of the two or a d_level that cannot hold
+    nframes * (nsyms - 1) floats"""
+    if rule not in (SOFT_PER_CARRIER, SOFT_PER_SYMBOL):
+        raise ValueError("rule must be SOFT_PER_CARRIER or SOFT_PER_SYMBOL: %r" % (rule,))
+    if d_level is not None and (not d_level.is_cuda or str(d_level.dtype) != "torch.float32"
+                                or d_level.numel() < nframes * (shape.nsyms - 1)):
+        raise ValueError("d_level must be a float32 CUDA tensor of nframes * (nsyms - 1) elements")
+    return SoftRule(int(rule), float(gain))
+
+
+def ofdm_demap_soft_dev(d_fft, shape, d_bins, rule, gain, nframes, d_fic=None, d_ring=None, first_row=0, col=0,
+                        d_level=None, sym_stride=None, frame_stride=None, stream=None):
+    """Channel-state weighting (include/viterbi_amd.h): ofdm_demap_dev with a soft-decision rule in the place of its gain.
+    rule SOFT_PER_SYMBOL scales a symbol's carriers by the symbol's mean level (gain 64 ... 128 suits the decoders);
+    SOFT_PER_CARRIER is ofdm_demap_dev itself.  d_level: optional float32 CUDA tensor of nframes * (nsyms - 1) elements
+    that receives every demapped symbol's level (SOFT_PER_SYMBOL only)."""
+    if not isinstance(shape, OfdmShape):
+        shape = OfdmShape(*[int(v) for v in shape])
+    soft = _soft_rule(rule, gain, d_level, shape, nframes)
+    if not d_fft.is_cuda or str(d_fft.dtype) not in ("torch.complex64", "torch.float32"):
+        raise ValueError("d_fft must be a complex64 or float32 CUDA tensor")
+    if not d_bins.is_cuda or d_bins.element_size() != 2:
+        raise ValueError("d_bins must be a CUDA tensor of 2-byte elements (uint16 bins)")
+    if sym_stride is None:
+        sym_stride = shape.nfft
+    if frame_stride is None:
+        frame_stride = shape.nsyms * sym_stride
+    ring = None if d_ring is None else C.byref(cif_ring(d_ring, first_row))
+    _check(lib().vit_ofdm_demap_soft_dev(_ptr(d_fft), sym_stride, frame_stride, _ptr(d_bins), C.byref(shape), C.byref(soft),
+                                         nframes, _ptr(d_fic), ring, col, _ptr(d_level), _stream_ptr(stream)),
+           "vit_ofdm_demap_soft_dev")
+
+
+def ofdm_demod_soft_dev(d_iq, shape, d_bins, rule, gain, nframes, d_tw, sym_stride, frame_stride=None, d_start=None,
+                        d_nco=None, nco_bits=0, d_rot=None, d_fic=None, d_ring=None, first_row=0, col=0, d_level=None,
+                        stream=None, nsamples=None, iq_format=IQ_F32, iq_scale=1.0):
+    """Channel-state weighting (include/viterbi_amd.h): ofdm_demod_dev with a soft-decision rule in the place of its gain;
+    rule, gain and d_level as ofdm_demap_soft_dev, every other argument as ofdm_demod_dev (integer sample formats
+    included)."""
+    if not isinstance(shape, OfdmShape):
+        shape = OfdmShape(*[int(v) for v in shape])
+    soft = _soft_rule(rule, gain, d_level, shape, nframes)
+    if not d_bins.is_cuda or d_bins.element_size() != 2:
+        raise ValueError("d_bins must be a CUDA tensor of 2-byte elements (uint16 bins)")
+    if frame_stride is None and d_start is None:
+        raise ValueError("frame_stride or d_start is required")
+    inp = iq_input(d_iq, d_tw, sym_stride, frame_stride, d_start, d_nco, nco_bits, d_rot, nsamples, iq_format)
+    ring = None if d_ring is None else C.byref(cif_ring(d_ring, first_row))
+    fmt = None if iq_format == IQ_F32 else C.byref(IqFormat(int(iq_format), float(iq_scale)))
+    _check(lib().vit_ofdm_demod_soft_dev(C.byref(inp), fmt, _ptr(d_bins), C.byref(shape), C.byref(soft), nframes, _ptr(d_fic),
+                                         ring, col, _ptr(d_level), _stream_ptr(stream)), "vit_ofdm_demod_soft_dev")
 
 
 def ofdm_sync_dev(d_iq, nfft, nsyms, nframes, d_tw, sym_stride, d_nco, nco_bits, d_prs, d_start_out, d_rot_out, W, M,

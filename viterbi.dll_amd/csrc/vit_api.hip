@@ -1324,11 +1324,35 @@ static int ofdm_check_outputs(const char* who, const vit_ofdm_shape* shape, floa
     return VIT_OK;
 }
 
-int vit_ofdm_demap_dev(const float* d_fft, uint64_t sym_stride, uint64_t frame_stride, const uint16_t* d_bins,
-                       const vit_ofdm_shape* shape, float gain, int64_t nframes, uint8_t* d_fic, const vit_cif_ring* ring,
-                       uint64_t col, void* stream) {
-    const char* who = "vit_ofdm_demap_dev";
-    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+// the rules of vit_soft_rule (after VIT_ERR_NO_DEVICE): on VIT_OK *gain is the rule's gain, still to pass ofdm_check_outputs
+static int ofdm_check_soft(const char* who, const vit_soft_rule* soft, const float* d_level, float* gain) {
+    if (!soft) {
+        set_err("%s: bad arguments (NULL soft)", who);
+        return VIT_ERR_ARG;
+    }
+    if (soft->rule != VIT_SOFT_PER_CARRIER && soft->rule != VIT_SOFT_PER_SYMBOL) {
+        set_err("%s: bad arguments (rule %u, VIT_SOFT_PER_CARRIER or VIT_SOFT_PER_SYMBOL)", who, soft->rule);
+        return VIT_ERR_ARG;
+    }
+    if (soft->rule == VIT_SOFT_PER_CARRIER && d_level) {
+        set_err("%s: bad arguments (d_level needs VIT_SOFT_PER_SYMBOL: the per-carrier rule forms no level)", who);
+        return VIT_ERR_ARG;
+    }
+    if (soft->rule == VIT_SOFT_PER_SYMBOL && !(soft->gain >= 0x1p-24f && soft->gain <= 65536.0f)) {  // false for NaN
+        set_err("%s: bad arguments (gain %g, 2^-24 <= gain <= 65536 for VIT_SOFT_PER_SYMBOL)", who, (double)soft->gain);
+        return VIT_ERR_ARG;
+    }
+    if (((uintptr_t)d_level & 3u) != 0) {
+        set_err("%s: bad arguments (d_level must be 4-byte aligned)", who);
+        return VIT_ERR_ARG;
+    }
+    *gain = soft->gain;
+    return VIT_OK;
+}
+
+static int ofdm_demap(const char* who, const float* d_fft, uint64_t sym_stride, uint64_t frame_stride, const uint16_t* d_bins,
+                      const vit_ofdm_shape* shape, float gain, uint32_t rule, int64_t nframes, uint8_t* d_fic,
+                      const vit_cif_ring* ring, uint64_t col, float* d_level, void* stream) {
     if (!d_fft || !d_bins || !shape || nframes < 0) {
         set_err("%s: bad arguments (NULL d_fft, d_bins or shape, or nframes=%lld < 0)", who, (long long)nframes);
         return VIT_ERR_ARG;
@@ -1341,10 +1365,29 @@ int vit_ofdm_demap_dev(const float* d_fft, uint64_t sym_stride, uint64_t frame_s
         return VIT_ERR_ARG;
     }
     if (nframes == 0) return VIT_OK;
-    hipError_t e = vit_launch_ofdm_demap(d_fft, sym_stride, frame_stride, d_bins, sh, gain, nframes, d_fic, ring, col,
-                                         (hipStream_t)stream);
+    hipError_t e = vit_launch_ofdm_demap(d_fft, sym_stride, frame_stride, d_bins, sh, gain, nframes, d_fic, ring, col, rule,
+                                         d_level, (hipStream_t)stream);
     if (e != hipSuccess) { set_err("OFDM demap launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
     return VIT_OK;
+}
+
+int vit_ofdm_demap_dev(const float* d_fft, uint64_t sym_stride, uint64_t frame_stride, const uint16_t* d_bins,
+                       const vit_ofdm_shape* shape, float gain, int64_t nframes, uint8_t* d_fic, const vit_cif_ring* ring,
+                       uint64_t col, void* stream) {
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    return ofdm_demap("vit_ofdm_demap_dev", d_fft, sym_stride, frame_stride, d_bins, shape, gain, VIT_SOFT_PER_CARRIER, nframes,
+                      d_fic, ring, col, nullptr, stream);
+}
+
+int vit_ofdm_demap_soft_dev(const float* d_fft, uint64_t sym_stride, uint64_t frame_stride, const uint16_t* d_bins,
+                            const vit_ofdm_shape* shape, const vit_soft_rule* soft, int64_t nframes, uint8_t* d_fic,
+                            const vit_cif_ring* ring, uint64_t col, float* d_level, void* stream) {
+    const char* who = "vit_ofdm_demap_soft_dev";
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    float gain = 0.0f;
+    if (ofdm_check_soft(who, soft, d_level, &gain) != VIT_OK) return VIT_ERR_ARG;
+    return ofdm_demap(who, d_fft, sym_stride, frame_stride, d_bins, shape, gain, soft->rule, nframes, d_fic, ring, col, d_level,
+                      stream);
 }
 
 // ---- from the samples: rotation, FFT and the demapping behind it (vit_ofdm_td.hip) --------------------------------------
@@ -1452,10 +1495,10 @@ int vit_ofdm_fft_iq_dev(const vit_iq_input* in, const vit_iq_format* fmt, uint32
     return ofdm_fft("vit_ofdm_fft_iq_dev", in, fmt, nfft, nsyms, nframes, d_fft, out_sym_stride, out_frame_stride, stream);
 }
 
+// the three demodulator entries behind their VIT_ERR_NO_DEVICE answer; rule and d_level as vit_launch_ofdm_demod takes them
 static int ofdm_demod(const char* who, const vit_iq_input* in, const vit_iq_format* fmt, const uint16_t* d_bins,
                       const vit_ofdm_shape* shape, float gain, int64_t nframes, uint8_t* d_fic, const vit_cif_ring* ring,
-                      uint64_t col, void* stream) {
-    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+                      uint64_t col, uint32_t rule, float* d_level, void* stream) {
     if (iq_check_format(who, fmt) != VIT_OK) return VIT_ERR_ARG;
     if (!d_bins || !shape || nframes < 0) {
         set_err("%s: bad arguments (NULL d_bins or shape, or nframes=%lld < 0)", who, (long long)nframes);
@@ -1464,19 +1507,33 @@ static int ofdm_demod(const char* who, const vit_iq_input* in, const vit_iq_form
     if (ofdm_check_outputs(who, shape, gain, nframes, d_fic, ring, col) != VIT_OK) return VIT_ERR_ARG;
     if (ofdm_check_input(who, in, fmt, shape->nfft, shape->nsyms, nframes) != VIT_OK) return VIT_ERR_ARG;
     if (nframes == 0) return VIT_OK;
-    hipError_t e = vit_launch_ofdm_demod(*in, *fmt, d_bins, *shape, gain, nframes, d_fic, ring, col, (hipStream_t)stream);
+    hipError_t e = vit_launch_ofdm_demod(*in, *fmt, d_bins, *shape, gain, nframes, d_fic, ring, col, rule, d_level, (hipStream_t)stream);
     if (e != hipSuccess) { set_err("OFDM demodulation launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
     return VIT_OK;
 }
 
 int vit_ofdm_demod_dev(const vit_iq_input* in, const uint16_t* d_bins, const vit_ofdm_shape* shape, float gain, int64_t nframes,
                        uint8_t* d_fic, const vit_cif_ring* ring, uint64_t col, void* stream) {
-    return ofdm_demod("vit_ofdm_demod_dev", in, &IQ_FORMAT_F32, d_bins, shape, gain, nframes, d_fic, ring, col, stream);
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    return ofdm_demod("vit_ofdm_demod_dev", in, &IQ_FORMAT_F32, d_bins, shape, gain, nframes, d_fic, ring, col, VIT_SOFT_PER_CARRIER,
+                      nullptr, stream);
 }
 
 int vit_ofdm_demod_iq_dev(const vit_iq_input* in, const vit_iq_format* fmt, const uint16_t* d_bins, const vit_ofdm_shape* shape,
                           float gain, int64_t nframes, uint8_t* d_fic, const vit_cif_ring* ring, uint64_t col, void* stream) {
-    return ofdm_demod("vit_ofdm_demod_iq_dev", in, fmt, d_bins, shape, gain, nframes, d_fic, ring, col, stream);
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    return ofdm_demod("vit_ofdm_demod_iq_dev", in, fmt, d_bins, shape, gain, nframes, d_fic, ring, col, VIT_SOFT_PER_CARRIER, nullptr,
+                      stream);
+}
+
+int vit_ofdm_demod_soft_dev(const vit_iq_input* in, const vit_iq_format* fmt, const uint16_t* d_bins, const vit_ofdm_shape* shape,
+                            const vit_soft_rule* soft, int64_t nframes, uint8_t* d_fic, const vit_cif_ring* ring, uint64_t col,
+                            float* d_level, void* stream) {
+    const char* who = "vit_ofdm_demod_soft_dev";
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    float gain = 0.0f;
+    if (ofdm_check_soft(who, soft, d_level, &gain) != VIT_OK) return VIT_ERR_ARG;
+    return ofdm_demod(who, in, fmt ? fmt : &IQ_FORMAT_F32, d_bins, shape, gain, nframes, d_fic, ring, col, soft->rule, d_level, stream);
 }
 
 // ---- from the coarse start: fine time and frequency (vit_ofdm_sync.hip) ----------------------------------------------------

@@ -93,10 +93,11 @@ hipError_t vit_launch_depunct_ti(const vit_cif_ring& ring, uint64_t col, uint8_t
 // vit_freq_interleave_bins): K = 3*nfft/4 bins to h_bins, or -1.
 int64_t vit_freq_bins_host(uint32_t nfft, uint16_t* h_bins);
 // Demaps nframes transmission frames; the caller has checked every argument rule of vit_ofdm_demap_dev.  d_fic / ring may
-// be NULL (those symbols are skipped).
+// be NULL (those symbols are skipped).  rule: VIT_SOFT_PER_CARRIER (the existing kernels; d_level NULL) or
+// VIT_SOFT_PER_SYMBOL (the kernels of the per-symbol rule; d_level NULL or nframes * (nsyms-1) floats).
 hipError_t vit_launch_ofdm_demap(const float* d_fft, uint64_t sym_stride, uint64_t frame_stride, const uint16_t* d_bins,
                                  const vit_ofdm_shape& shape, float gain, int64_t nframes, uint8_t* d_fic,
-                                 const vit_cif_ring* ring, uint64_t col, hipStream_t stream);
+                                 const vit_cif_ring* ring, uint64_t col, uint32_t rule, float* d_level, hipStream_t stream);
 // From the samples (vit_ofdm_td.hip).  The tables of include/viterbi_amd.h: pairs written, or -1.
 int64_t vit_fft_twiddles_host(uint32_t nfft, float* h_tw);
 int64_t vit_nco_table_host(uint32_t nco_bits, float* h_nco);
@@ -106,7 +107,8 @@ int64_t vit_nco_table_host(uint32_t nco_bits, float* h_nco);
 hipError_t vit_launch_ofdm_fft(const vit_iq_input& in, const vit_iq_format& fmt, uint32_t nfft, uint32_t nsyms, int64_t nframes, float* d_fft,
                                uint64_t out_sym_stride, uint64_t out_frame_stride, hipStream_t stream);
 hipError_t vit_launch_ofdm_demod(const vit_iq_input& in, const vit_iq_format& fmt, const uint16_t* d_bins, const vit_ofdm_shape& shape, float gain,
-                                 int64_t nframes, uint8_t* d_fic, const vit_cif_ring* ring, uint64_t col, hipStream_t stream);
+                                 int64_t nframes, uint8_t* d_fic, const vit_cif_ring* ring, uint64_t col, uint32_t rule, float* d_level,
+                                 hipStream_t stream);
 // From the coarse start (vit_ofdm_sync.hip): one workgroup per frame; the caller has checked every argument rule.
 hipError_t vit_launch_ofdm_sync(const vit_iq_input& in, const vit_iq_format& fmt, const vit_sync_params& p, const float* d_prs, int64_t nframes,
                                 int64_t* d_start_out, uint32_t* d_rot_out, uint32_t* d_info, hipStream_t stream);

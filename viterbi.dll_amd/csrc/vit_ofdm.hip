@@ -18,6 +18,7 @@
 #pragma clang fp contract(off)
 #include <cfloat>
 
+#include "vit_csi_dev.h"
 #include "vit_internal.h"
 
 namespace {
@@ -169,9 +170,179 @@ __global__ __launch_bounds__(TPB) void vit_ofdm_demap_kernel(OfdmArgs A) {
     }
 }
 
+// ---- VIT_SOFT_PER_SYMBOL (include/viterbi_amd.h, "Channel-state weighting") ------------------------------------------
+// A kernel beside the one above, which stays what it was.  A symbol is demapped in two halves around its level S:
+//   1. re, im and nrm of the lane's carriers; re and im stay in the lane's registers (0 for an erasure), the term of the
+//      sum goes to position n of a float array in LDS; the chunk of b is dead and receives the next row, as above;
+//   2. the first A = max(64, nfft/8) threads are the header's accumulators: thread i reads groups i and i + A of 4
+//      consecutive n (one 16-byte LDS load each), the wavefronts reduce (vit_csi_dev.h) and leave their totals in LDS;
+//   3. every thread finishes the tree, forms s, quantises its carriers into the tile; the tile leaves as above.
+// Three barriers per symbol instead of one.  LDS: the kernel above's, then 4*ceil(K/4) floats and CSI_PARTS totals.
+struct SoftArgs {
+    float* level;  // d_level or nullptr
+    u32 nlev;      // its words per frame: nsyms - 1
+};
+
 template <u32 TPB, u32 CPL>
-hipError_t launch(const OfdmArgs& A, u64 grid, size_t lds, hipStream_t stream) {
-    hipLaunchKernelGGL((vit_ofdm_demap_kernel<TPB, CPL>), dim3((unsigned)grid), dim3(TPB), lds, stream, A);
+struct Prod {
+    float4 y[CPL];  // (re, im) of the chunk's two bins
+};
+
+template <u32 TPB, u32 CPL>
+__device__ __forceinline__ void soft_products(const Row<TPB, CPL>& a, Row<TPB, CPL>& b, const float4* next, u32 lane_off,
+                                              u32 used, const u32* inv2, float* term, Prod<TPB, CPL>& p) {
+#pragma unroll
+    for (u32 j = 0; j < CPL; j++) {
+        p.y[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!(used >> j & 1u)) continue;
+        const u32 ent = inv2[threadIdx.x + j * TPB], n0 = ent & 0xFFFFu, n1 = ent >> 16;  // n of the two bins
+        if (n0 != UNUSED) {
+            const float re = a.v[j].x * b.v[j].x + a.v[j].y * b.v[j].y;
+            const float im = a.v[j].y * b.v[j].x - a.v[j].x * b.v[j].y;
+            const float v = vit_csi::csi_term(__builtin_fabsf(re) + __builtin_fabsf(im));
+            term[n0] = v;
+            if (v != 0.0f) {
+                p.y[j].x = re;
+                p.y[j].y = im;
+            }
+        }
+        if (n1 != UNUSED) {
+            const float re = a.v[j].z * b.v[j].z + a.v[j].w * b.v[j].w;
+            const float im = a.v[j].w * b.v[j].z - a.v[j].z * b.v[j].w;
+            const float v = vit_csi::csi_term(__builtin_fabsf(re) + __builtin_fabsf(im));
+            term[n1] = v;
+            if (v != 0.0f) {
+                p.y[j].z = re;
+                p.y[j].w = im;
+            }
+        }
+        if (next) b.v[j] = load_chunk<TPB>(next, j, lane_off);
+    }
+}
+
+// LDS: two tiles of tb bytes, nfft u16 of the inverted table, K4 = 4*ceil(K/4) terms, CSI_PARTS wavefront totals.
+template <u32 TPB, u32 CPL>
+__global__ __launch_bounds__(TPB) void vit_ofdm_demap_soft_kernel(OfdmArgs A, SoftArgs L) {
+    extern __shared__ uint4 lds_ofdm[];
+    const u32 K = A.K, nb = 2u * K, tb = (nb + 15u) / 16u * 16u, ngroups = (K + 3u) / 4u;
+    const u32 NA = A.nfft / 8u < 64u ? 64u : A.nfft / 8u;  // accumulators: NA <= TPB, whole wavefronts
+    uint8_t* tiles = reinterpret_cast<uint8_t*>(lds_ofdm);
+    uint16_t* inv = reinterpret_cast<uint16_t*>(tiles + 2u * tb);
+    float* term = reinterpret_cast<float*>(tiles + 2u * tb + 2u * A.nfft);  // 16-byte aligned: nfft >= 64
+    float* part = term + 4u * ngroups;
+    const u64 t = blockIdx.x / A.runs;
+    const u32 s0 = A.lo + (u32)(blockIdx.x % A.runs) * A.run, s1 = s0 + A.run < A.hi ? s0 + A.run : A.hi;
+
+    for (u32 i = threadIdx.x; i < A.nfft / 2u; i += TPB) reinterpret_cast<u32*>(inv)[i] = UNUSED | UNUSED << 16;
+    for (u32 i = threadIdx.x; i < 2u * tb / 4u; i += TPB) reinterpret_cast<u32*>(tiles)[i] = 0x80808080u;
+    for (u32 i = threadIdx.x; i < 4u * ngroups + vit_csi::CSI_PARTS; i += TPB) term[i] = 0.0f;  // an n nobody owns adds +0
+    __syncthreads();
+    for (u32 n = threadIdx.x; n < K; n += TPB) {
+        const u32 b = A.bins[n];
+        if (b < A.nfft) inv[b] = (uint16_t)n;
+    }
+    __syncthreads();
+    const u32* inv2 = reinterpret_cast<const u32*>(inv);
+    u32 used = 0;
+#pragma unroll
+    for (u32 j = 0; j < CPL; j++) {
+        const u32 c = threadIdx.x + j * TPB;
+        if (2u * c < A.nfft && inv2[c] != 0xFFFFFFFFu) used |= 1u << j;
+    }
+    const u32 lane_off = threadIdx.x * 16u;
+    const float4* frame = A.fft + t * A.frame_stride2;
+    Row<TPB, CPL> x, y;  // rows s and s + 1 at even s - s0, rows s + 1 and s at odd
+    load_row(frame + (u64)s0 * A.sym_stride2, lane_off, used, x);
+    load_row(frame + (u64)(s0 + 1u) * A.sym_stride2, lane_off, used, y);
+    for (u32 s = s0; s < s1; s++) {
+        uint8_t* tile = tiles + (s & 1u) * tb;
+        const float4* next = s + 1u < s1 ? frame + (u64)(s + 2u) * A.sym_stride2 : nullptr;
+        Prod<TPB, CPL> p;
+        if ((s - s0) & 1u)
+            soft_products(x, y, next, lane_off, used, inv2, term, p);
+        else
+            soft_products(y, x, next, lane_off, used, inv2, term, p);
+        __syncthreads();
+        if (threadIdx.x < NA) {  // whole wavefronts
+            const u32 g0 = threadIdx.x, g1 = threadIdx.x + NA;
+            float acc = 0.0f;
+            if (g0 < ngroups) {
+                const float4 v = reinterpret_cast<const float4*>(term)[g0];
+                acc = vit_csi::csi_group(v.x, v.y, v.z, v.w);
+            }
+            if (g1 < ngroups) {
+                const float4 v = reinterpret_cast<const float4*>(term)[g1];
+                acc = acc + vit_csi::csi_group(v.x, v.y, v.z, v.w);
+            }
+            acc = vit_csi::csi_wave_sum(acc);
+            if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = acc;
+        }
+        __syncthreads();
+        const float S = vit_csi::csi_block_sum<TPB / 64u>(part);
+        const float sc = vit_csi::csi_scale(S, A.gain, K);
+        if (threadIdx.x == 0 && L.level) L.level[t * L.nlev + s] = S;
+#pragma unroll
+        for (u32 j = 0; j < CPL; j++) {
+            if (!(used >> j & 1u)) continue;
+            const u32 ent = inv2[threadIdx.x + j * TPB], n0 = ent & 0xFFFFu, n1 = ent >> 16;
+            if (n0 != UNUSED) {
+                const u32 q = vit_csi::csi_pair(p.y[j].x, p.y[j].y, sc);
+                tile[n0] = (uint8_t)q;
+                tile[K + n0] = (uint8_t)(q >> 8);
+            }
+            if (n1 != UNUSED) {
+                const u32 q = vit_csi::csi_pair(p.y[j].z, p.y[j].w, sc);
+                tile[n1] = (uint8_t)q;
+                tile[K + n1] = (uint8_t)(q >> 8);
+            }
+        }
+        __syncthreads();
+        // The tile's nb bytes to their place: d_fic, or a CIF row of the ring.  The kernel above's lines, repeated: moved
+        // into a function that both call, they cost three of its five instantiations a VGPR (27 -> 28, 39 -> 40, 63 -> 64),
+        // and that kernel stays what it was measured with (as vit_ofdm_td.hip keeps its pass loops beside vit_fft_dev.h).
+        uint8_t* dst;
+        if (s < A.fic_syms) {
+            dst = A.fic + (t * A.fic_syms + s) * nb;
+        } else {
+            const u32 m = s - A.fic_syms, c = m / A.per;
+            u64 row = A.first_row + t * A.cifs + c;
+            if (row >= A.nrows) row -= A.nrows;
+            dst = A.ring + row * A.row_bytes + A.col + (u64)(m - c * A.per) * nb;
+        }
+        if (nb >= 16u) {
+            for (u32 e = threadIdx.x; e < tb / 16u; e += TPB) {
+                const u32 want = 16u * e, a = want < nb - 16u ? want : nb - 16u;  // the last chunk ends at the tile's end
+                uint4 v;
+                if (a == want) {
+                    v = *reinterpret_cast<const uint4*>(tile + a);
+                } else {
+                    u32 w[4] = {0, 0, 0, 0};
+#pragma unroll
+                    for (u32 k = 0; k < 16; k++) w[k >> 2] |= (u32)tile[a + k] << (8u * (k & 3u));
+                    v = make_uint4(w[0], w[1], w[2], w[3]);
+                }
+                __builtin_memcpy(dst + a, &v, 16);  // unaligned global_store_dwordx4
+            }
+        } else if (threadIdx.x < nb) {
+            dst[threadIdx.x] = tile[threadIdx.x];
+        }
+    }
+}
+
+template <u32 TPB, u32 CPL>
+hipError_t launch(const OfdmArgs& A, const SoftArgs* L, u64 grid, size_t lds, hipStream_t stream) {
+    if (L) {
+        if (lds > 64u * 1024u) {  // nfft 8192 with K > 4080: the terms take the kernel past the default limit
+            static uint64_t optin_done = 0;
+            int dev = 0;
+            if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+            const void* ks[1] = {reinterpret_cast<const void*>(&vit_ofdm_demap_soft_kernel<TPB, CPL>)};
+            const hipError_t e = vit_optin_dynamic_lds(ks, 1, 160 * 1024, dev, &optin_done);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL((vit_ofdm_demap_soft_kernel<TPB, CPL>), dim3((unsigned)grid), dim3(TPB), lds, stream, A, *L);
+    } else
+        hipLaunchKernelGGL((vit_ofdm_demap_kernel<TPB, CPL>), dim3((unsigned)grid), dim3(TPB), lds, stream, A);
     return hipGetLastError();
 }
 
@@ -190,7 +361,7 @@ int64_t vit_freq_bins_host(uint32_t nfft, uint16_t* h_bins) {
 
 hipError_t vit_launch_ofdm_demap(const float* d_fft, uint64_t sym_stride, uint64_t frame_stride, const uint16_t* d_bins,
                                  const vit_ofdm_shape& shape, float gain, int64_t nframes, uint8_t* d_fic,
-                                 const vit_cif_ring* ring, uint64_t col, hipStream_t stream) {
+                                 const vit_cif_ring* ring, uint64_t col, uint32_t rule, float* d_level, hipStream_t stream) {
     OfdmArgs A = {};
     A.fft = reinterpret_cast<const float4*>(d_fft);
     A.sym_stride2 = sym_stride / 2u;
@@ -226,11 +397,13 @@ hipError_t vit_launch_ofdm_demap(const float* d_fft, uint64_t sym_stride, uint64
     A.runs = (nsym + run - 1) / run;
     const u64 grid = (u64)nframes * A.runs;
     if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const size_t lds = 2u * (size_t)((2u * A.K + 15u) / 16u * 16u) + 2u * (size_t)A.nfft;
+    size_t lds = 2u * (size_t)((2u * A.K + 15u) / 16u * 16u) + 2u * (size_t)A.nfft;
+    const SoftArgs soft = {d_level, shape.nsyms - 1u}, *L = rule == VIT_SOFT_PER_SYMBOL ? &soft : nullptr;
+    if (L) lds += 4u * (size_t)((A.K + 3u) / 4u * 4u + vit_csi::CSI_PARTS);  // at most 80 KiB + 64 (nfft = K = 8192)
     const u32 chunks = A.nfft / 2u;
-    if (chunks <= 256u) return launch<256, 1>(A, grid, lds, stream);
-    if (chunks <= 512u) return launch<256, 2>(A, grid, lds, stream);
-    if (chunks <= 1024u) return launch<256, 4>(A, grid, lds, stream);
-    if (chunks <= 2048u) return launch<1024, 2>(A, grid, lds, stream);
-    return launch<1024, 4>(A, grid, lds, stream);
+    if (chunks <= 256u) return launch<256, 1>(A, L, grid, lds, stream);
+    if (chunks <= 512u) return launch<256, 2>(A, L, grid, lds, stream);
+    if (chunks <= 1024u) return launch<256, 4>(A, L, grid, lds, stream);
+    if (chunks <= 2048u) return launch<1024, 2>(A, L, grid, lds, stream);
+    return launch<1024, 4>(A, L, grid, lds, stream);
 }

@@ -22,10 +22,15 @@
 // Integer sample formats (vit_iq_dev.h): one template flag apart from the float32 instantiations, which stay what they
 // were.  The prefetched samples are then kept raw, 8 dwords instead of 16, and converted where the first pass consumes
 // them; the three formats share an instantiation and part in two scalar branches of the loader.
+// The per-symbol soft-decision rule (VIT_SOFT_PER_SYMBOL, vit_csi_dev.h): one more template flag, the other instantiations
+// stay what they were.  The thread's groups T + j*TPB are the header's groups of accumulator T (TPB = max(64, nfft/8)), so
+// it keeps re and im of its 8 carriers, sums their terms, the workgroup reduces (DPP inside a wavefront, one LDS exchange
+// and one barrier across them, CSI_PARTS floats behind the twiddles) and every thread quantises with the symbol's scale.
 #pragma clang fp contract(off)
 #include <cfloat>
 #include <cmath>
 
+#include "vit_csi_dev.h"
 #include "vit_fft_dev.h"
 #include "vit_internal.h"
 #include "vit_iq_dev.h"
@@ -58,6 +63,9 @@ struct TdArgs {
     // integer sample formats: iq then points at samples of iq_fmt (VIT_IQ_CU8 ... VIT_IQ_CS16)
     u32 iq_fmt;
     float iq_scale;
+    // the per-symbol rule: d_level or nullptr, its words per frame (nsyms - 1)
+    float* level;
+    u32 nlev, csi;  // csi: host side only, picks the instantiation
 };
 
 
@@ -110,7 +118,7 @@ __device__ __forceinline__ void load_samples(const TdArgs& A, const void* frame,
         }
 }
 
-template <u32 M, bool ROT, bool DEMAP, bool INT>
+template <u32 M, bool ROT, bool DEMAP, bool INT, bool CSI = false>
 __global__ __launch_bounds__(Cfg<M>::TPB) __attribute__((amdgpu_waves_per_eu(Cfg<M>::waves(ROT), Cfg<M>::waves(ROT)))) void vit_ofdm_td_kernel(TdArgs A) {
     typedef Cfg<M> C;
     constexpr u32 N = C::N, TA = C::TA, R1 = C::R1, R = 1u << R1, NP = C::NP;
@@ -139,6 +147,8 @@ __global__ __launch_bounds__(Cfg<M>::TPB) __attribute__((amdgpu_waves_per_eu(Cfg
     static_assert(pad_is_affine(M), "pad() must skew every thread's group alike");
     float2* tw_lds = lds_td + Cfg<M>::PADN;
     for (u32 i = T; i < N / 2u; i += C::TPB) tw_lds[twpad(i)] = A.tw[i];
+    float* part = reinterpret_cast<float*>(lds_td) + C::LDS_BYTES / 4u;  // CSI: the wavefronts' totals, +0 behind the last
+    if (CSI && T < vit_csi::CSI_PARTS) part[T] = 0.0f;
     float2 e1 = make_float2(1.f, 0.f), e3 = e1;
     if (R1 == 3) {
         e1 = A.tw[N / 8u];
@@ -214,19 +224,59 @@ __global__ __launch_bounds__(Cfg<M>::TPB) __attribute__((amdgpu_waves_per_eu(Cfg
                     dst = A.ring + row * A.row_bytes + A.col + (u64)(m - c * A.per) * 2u * A.K;
                 }
             }
+            float yre[CSI ? C::CG : 1][4], yim[CSI ? C::CG : 1][4], sc = 0.0f;
+            if constexpr (CSI) {
+                // re, im of the thread's carriers (0 for an erasure) and accumulator T of the symbol's level
+                float acc = 0.0f;
+#pragma unroll
+                for (u32 j = 0; j < C::CG; j++) {
+                    float v[4];
+#pragma unroll
+                    for (u32 c = 0; c < 4; c++) {
+                        const bool named = bin[j][c] < N;
+                        const float2 a = named ? lds_td[pad(bin[j][c])] : make_float2(0.f, 0.f);
+                        const float2 b = prev[j][c];
+                        const float re = a.x * b.x + a.y * b.y;
+                        const float im = a.y * b.x - a.x * b.y;
+                        v[c] = named ? vit_csi::csi_term(__builtin_fabsf(re) + __builtin_fabsf(im)) : 0.0f;
+                        yre[j][c] = v[c] != 0.0f ? re : 0.0f;
+                        yim[j][c] = v[c] != 0.0f ? im : 0.0f;
+                        prev[j][c] = a;
+                    }
+                    const float q = vit_csi::csi_group(v[0], v[1], v[2], v[3]);
+                    acc = j ? acc + q : q;  // a group at or beyond K adds +0
+                }
+                if (dst) {  // uniform: every symbol of the run but the one before it
+                    acc = vit_csi::csi_wave_sum(acc);
+                    if ((T & 63u) == 0) part[T >> 6] = acc;
+                    __syncthreads();
+                    const float S = vit_csi::csi_block_sum<C::TPB / 64u>(part);
+                    sc = vit_csi::csi_scale(S, A.gain, A.K);
+                    if (T == 0 && A.level) A.level[t * A.nlev + s] = S;
+                }
+            }
 #pragma unroll
             for (u32 j = 0; j < C::CG; j++) {
                 const u32 n0 = 4u * (T + j * C::TPB);
                 if (n0 >= A.K) continue;
                 u32 lo4 = 0, hi4 = 0;
+                if constexpr (CSI) {
 #pragma unroll
-                for (u32 c = 0; c < 4; c++) {
-                    const bool named = bin[j][c] < N;
-                    const float2 a = named ? lds_td[pad(bin[j][c])] : make_float2(0.f, 0.f);
-                    const u32 q = named && dst ? soft_pair(a.x, a.y, prev[j][c].x, prev[j][c].y, A.gain) : 0x8080u;
-                    lo4 |= (q & 0xFFu) << (8u * c);
-                    hi4 |= (q >> 8) << (8u * c);
-                    prev[j][c] = a;
+                    for (u32 c = 0; c < 4; c++) {
+                        const u32 q = vit_csi::csi_pair(yre[j][c], yim[j][c], sc);
+                        lo4 |= (q & 0xFFu) << (8u * c);
+                        hi4 |= (q >> 8) << (8u * c);
+                    }
+                } else {
+#pragma unroll
+                    for (u32 c = 0; c < 4; c++) {
+                        const bool named = bin[j][c] < N;
+                        const float2 a = named ? lds_td[pad(bin[j][c])] : make_float2(0.f, 0.f);
+                        const u32 q = named && dst ? soft_pair(a.x, a.y, prev[j][c].x, prev[j][c].y, A.gain) : 0x8080u;
+                        lo4 |= (q & 0xFFu) << (8u * c);
+                        hi4 |= (q >> 8) << (8u * c);
+                        prev[j][c] = a;
+                    }
                 }
                 if (!dst) continue;
                 if (n0 + 4u <= A.K) {
@@ -247,23 +297,24 @@ __global__ __launch_bounds__(Cfg<M>::TPB) __attribute__((amdgpu_waves_per_eu(Cfg
     }
 }
 
-template <u32 M, bool ROT, bool DEMAP, bool INT>
+template <u32 M, bool ROT, bool DEMAP, bool INT, bool CSI = false>
 hipError_t launch3(const TdArgs& A, u64 grid, hipStream_t stream) {
-    const size_t lds = Cfg<M>::LDS_BYTES;
+    const size_t lds = Cfg<M>::LDS_BYTES + (CSI ? 4u * vit_csi::CSI_PARTS : 0u);
     if (lds > 64u * 1024u) {
         static uint64_t optin_done = 0;
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        const void* ks[1] = {reinterpret_cast<const void*>(&vit_ofdm_td_kernel<M, ROT, DEMAP, INT>)};
+        const void* ks[1] = {reinterpret_cast<const void*>(&vit_ofdm_td_kernel<M, ROT, DEMAP, INT, CSI>)};
         const hipError_t e = vit_optin_dynamic_lds(ks, 1, 160 * 1024, dev, &optin_done);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((vit_ofdm_td_kernel<M, ROT, DEMAP, INT>), dim3((unsigned)grid), dim3(Cfg<M>::TPB), lds, stream, A);
+    hipLaunchKernelGGL((vit_ofdm_td_kernel<M, ROT, DEMAP, INT, CSI>), dim3((unsigned)grid), dim3(Cfg<M>::TPB), lds, stream, A);
     return hipGetLastError();
 }
 
 template <u32 M, bool INT>
 hipError_t launch2i(const TdArgs& A, bool demap, u64 grid, hipStream_t stream) {
+    if (demap && A.csi) return A.rot ? launch3<M, true, true, INT, true>(A, grid, stream) : launch3<M, false, true, INT, true>(A, grid, stream);
     if (A.rot) return demap ? launch3<M, true, true, INT>(A, grid, stream) : launch3<M, true, false, INT>(A, grid, stream);
     return demap ? launch3<M, false, true, INT>(A, grid, stream) : launch3<M, false, false, INT>(A, grid, stream);
 }
@@ -363,7 +414,8 @@ hipError_t vit_launch_ofdm_fft(const vit_iq_input& in, const vit_iq_format& fmt,
 }
 
 hipError_t vit_launch_ofdm_demod(const vit_iq_input& in, const vit_iq_format& fmt, const uint16_t* d_bins, const vit_ofdm_shape& shape, float gain,
-                                 int64_t nframes, uint8_t* d_fic, const vit_cif_ring* ring, uint64_t col, hipStream_t stream) {
+                                 int64_t nframes, uint8_t* d_fic, const vit_cif_ring* ring, uint64_t col, uint32_t rule, float* d_level,
+                                 hipStream_t stream) {
     TdArgs A = input_args(in, fmt, shape.nfft, shape.nsyms);
     A.bins = d_bins;
     A.K = shape.ncarriers;
@@ -374,6 +426,9 @@ hipError_t vit_launch_ofdm_demod(const vit_iq_input& in, const vit_iq_format& fm
     A.hi = ring ? shape.nsyms - 1u : shape.fic_syms;
     A.gain = gain;
     A.fic = d_fic;
+    A.csi = rule == VIT_SOFT_PER_SYMBOL;
+    A.level = d_level;
+    A.nlev = shape.nsyms - 1u;
     if (ring) {
         A.ring = const_cast<uint8_t*>(ring->d_base);  // this call is the ring's writer
         A.row_bytes = ring->row_bytes;
