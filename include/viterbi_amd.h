@@ -431,7 +431,7 @@ int vit_ofdm_demap_dev(const float *d_fft, uint64_t sym_stride, uint64_t frame_s
  * The two tables come from vit_ofdm_sync_dev ("From the coarse start", below) or from the caller's own estimator.
  * Integer samples as receivers deliver them go through the *_iq_dev calls ("Integer sample formats", below).
  * Channel-state weighting is a second soft-decision rule of both demappers ("Channel-state weighting", below).
- * Out of scope: first acquisition (finding the null symbol), resampling. */
+ * First acquisition (finding the null symbol) is vit_ofdm_acquire_dev ("From the stream", below).  Out of scope: resampling. */
 typedef struct vit_iq_input {
     const float    *d_iq;         /* interleaved (re, im) float32 samples, 8-byte aligned (*_iq_dev: samples of fmt->format) */
     uint64_t        nsamples;     /* complex samples in d_iq: nothing at or beyond it is read */
@@ -498,8 +498,8 @@ int vit_ofdm_demod_dev(const vit_iq_input *in, const uint16_t *d_bins, const vit
  * tables vit_ofdm_demod_dev reads - d_start[t] and d_rot[t] = {phase0, step} - so nothing leaves the device between the
  * samples and the soft bytes.  It is the per-frame TRACKING step: it starts from a coarse start c that is right to within
  * +-W samples (the previous frame's start plus frame_stride, or the caller's null-symbol search) and a carrier offset of
- * less than M + 1/2 carrier spacings.  First acquisition (finding the null symbol in an unaligned stream) stays the
- * caller's.  The transmitted phase reference symbol is a caller-supplied DEVICE table d_prs: nfft complex binary32 values
+ * less than M + 1/2 carrier spacings.  First acquisition (finding the null symbol in an unaligned stream) is
+ * vit_ofdm_acquire_dev ("From the stream", below), which writes such a coarse table.  The transmitted phase reference symbol is a caller-supplied DEVICE table d_prs: nfft complex binary32 values
  * in FFT order, zero on unused bins (the library still holds no table of the standard except the bin table).
  * Like the rest of the front end the result is defined bit for bit. */
 typedef struct vit_sync_params {
@@ -613,6 +613,65 @@ int vit_ofdm_demod_iq_dev(const vit_iq_input *in, const vit_iq_format *fmt, cons
 int vit_ofdm_sync_iq_dev(const vit_iq_input *in, const vit_iq_format *fmt, const vit_sync_params *p, const float *d_prs,
                          int64_t nframes, int64_t *d_start_out, uint32_t *d_rot_out, uint32_t *d_info, void *stream);
 int vit_iq_convert_dev(const void *d_iq, const vit_iq_format *fmt, uint64_t nsamples, float *d_out, void *stream);
+
+/* From the stream: first acquisition.  What a receiver does first: it has an unaligned stream of samples and must find
+ * where the frames start.  One call searches one contiguous stream - float32, or an integer format of "Integer sample
+ * formats", which is why the section stands behind it - for the end of each null symbol, the edge where the power comes
+ * back, and writes for every frame period one coarse start into a DEVICE table of the kind vit_ofdm_sync_dev reads as
+ * in->d_start: samples -> acquire -> sync -> demod -> decode runs without a byte leaving the device.  It is an
+ * energy-edge detector and nothing more: no FFT, no correlation, so its starts are right to within about a block and
+ * vit_ofdm_sync_dev (W >= B) does the rest.  Like the rest of the front end the result is defined bit for bit. */
+typedef struct vit_acq_params {
+    uint32_t B;              /* block length, samples: a power of two 8 ... 512 */
+    uint32_t null_blocks;    /* Ln: blocks summed in front of a candidate edge, 1 ... 4096 (Ln*B <= the null symbol) */
+    uint32_t ref_blocks;     /* Lr: blocks summed behind it, 1 ... 4096 */
+    uint32_t period_blocks;  /* Pb: frame period in blocks, >= 1 (mode I at B 32: 6144) */
+    float    thr;            /* an edge is accepted when q <= thr; finite, > 0 */
+    uint32_t reserved;       /* 0 */
+    uint64_t first;          /* the search starts at this sample, <= nsamples; any position */
+    int64_t  offset;         /* added to the edge's sample index: e.g. guard + B/2 - backoff, the caller's choice */
+} vit_acq_params;
+/* Definition.  Every operation is one IEEE binary32 operation, rounded to nearest-even, in exactly this order, never
+ * contracted into an FMA.  x: the samples, components from the integer formats by the one-rounding rule of "Integer
+ * sample formats"; B, Ln, Lr, Pb, thr, first, offset: the struct's.
+ * A. Block power.  nblk = floor((nsamples - first) / B).  Sample i of block j is x[first + j*B + i]:
+ *      e[i] = fl( fl(re*re) + fl(im*im) )
+ *      p[j] = the tree of adjacent pairs over e[0 ... B-1]: v[i] = fl(v[2i] + v[2i+1]) until one value is left.
+ *    d_power, if given, receives p[0 ... nblk-1] and nothing else.
+ * B. Windows.  A candidate edge is a j with Ln <= j <= nblk - Lr: the edge lies between blocks j-1 and j.
+ *      N[j] = the sum of p[j-Ln+i], i = 0 ... Ln-1, in ascending i, into ONE accumulator that starts at +0: acc = fl(acc + p)
+ *      R[j] = the sum of p[j+i],    i = 0 ... Lr-1, in the same way
+ *      q[j] = fl(N[j] / R[j]) if R[j] > 0, else +Inf
+ * C. Search.  Period k = 0 ... nperiods-1 owns the candidates Ln + k*Pb <= j < Ln + (k+1)*Pb that exist.  j* is the LAST
+ *    minimum of q among them: in ascending j, a later j replaces the best when its q is less or equal.  (On a noise-free
+ *    stream every j whose front window lies in silence ties at q = 0; the last of them is the block that holds the
+ *    edge - the block behind it already has signal in N.)
+ * D. Outputs.  d_start_out[k] = first + j* * B + offset if the period has a candidate and q[j*] <= thr, else -1, which
+ *    vit_ofdm_sync_dev skips by its own rule.  d_info[4k ...] = {uint32 j* - (Ln + k*Pb), q[j*], N[j*], R[j*]} (optional:
+ *    q is the depth of the null, R / (Lr*B) the mean power behind the edge).  A period without candidates gets start -1
+ *    and info {0xFFFFFFFF, +Inf, 0, 0}.  Nothing outside the named words is written; no sample at or beyond nsamples and
+ *    none in front of `first` is read.
+ * The result depends on the samples and the struct alone: never on nperiods (period k has the same words in every call
+ * that reaches it), the launch or the device.
+ * Domain: every component of a sample is 0 or has a magnitude in [2^-40, 2^12].  Then nothing overflows and no denormal
+ * arises anywhere: a product fl(re*re) is 0 or in [2^-80, 2^24], so e is 0 or in [2^-80, 2^25]; all terms are
+ * non-negative, so a sum is 0 or at least its smallest nonzero term, 2^-80, and - rounding is monotone and the bounds
+ * are powers of two - at most its exact bound: p <= 512 * 2^25 = 2^34, N and R <= 4096 * 2^34 = 2^46.  With R >= 2^-80, q
+ * is 0 or lies in [2^-126, 2^126], a normal number.  An all-zero stream is inside the domain: every q is +Inf, j* is the
+ * period's last candidate, and every start is -1.  Outside the domain the outputs of the periods that read such samples
+ * are unspecified; nothing but the call's output words is written.  The caller keeps first + j* * B + offset inside int64.
+ * Arguments as the other *_dev calls: VIT_ERR_NO_DEVICE first; VIT_ERR_ARG (with vit_last_error()) for a NULL d_iq, p or
+ * d_start_out; a d_iq that is not aligned as in "Integer sample formats" (8 bytes for float32, 4 for an integer format), a
+ * d_start_out that is not 8-byte or a d_info or d_power that is not 4-byte aligned; every range in the struct's comments
+ * (thr NaN or Inf among them); a nonzero reserved; first > nsamples; nsamples >= 2^60; nperiods < 0; and the fmt rules of
+ * the *_iq_dev calls (an unknown format, a scale outside its range), except that a NULL fmt means float32.  Sample
+ * positions stay arbitrary: `first` may be odd, a CU8 block may start at an address that is 2 mod 4.  nperiods = 0 returns
+ * VIT_OK and writes nothing, d_power included.  Without d_power the powers live in a buffer of the calling thread, and
+ * only those the nperiods periods read are computed.  Everything is enqueued on `stream` without synchronising. */
+int vit_ofdm_acquire_dev(const void *d_iq, uint64_t nsamples, const vit_iq_format *fmt /* NULL: float32 */,
+                         const vit_acq_params *p, int64_t nperiods,
+                         int64_t *d_start_out, uint32_t *d_info /* optional, 4 words per period */,
+                         float *d_power /* optional, nblk floats */, void *stream);
 
 /* Channel-state weighting: a second soft-decision rule.  The definition of vit_ofdm_demap_dev scales every carrier by its
  * own |re| + |im|, so a carrier in a fading notch reaches the decoder with the confidence of the strongest one.  The

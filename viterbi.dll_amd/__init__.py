@@ -33,7 +33,7 @@ EXPORTS = [
     "vit_freq_interleave_bins", "vit_ofdm_demap_dev",
     "vit_fft_twiddles", "vit_nco_table", "vit_ofdm_fft_dev", "vit_ofdm_demod_dev", "vit_ofdm_sync_dev",
     "vit_ofdm_fft_iq_dev", "vit_ofdm_demod_iq_dev", "vit_ofdm_sync_iq_dev", "vit_iq_convert_dev",
-    "vit_ofdm_demap_soft_dev", "vit_ofdm_demod_soft_dev",
+    "vit_ofdm_demap_soft_dev", "vit_ofdm_demod_soft_dev", "vit_ofdm_acquire_dev",
     "vit_decode_stream_multi",
 ]
 MULTI_LOOPBACK = 0x1
@@ -110,6 +110,13 @@ class SyncParams(C.Structure):
     """vit_sync_params of include/viterbi_amd.h: SyncParams(nfft, nsyms, cp_symbols, W, M, thr, backoff, first_start)"""
     _fields_ = [("nfft", C.c_uint32), ("nsyms", C.c_uint32), ("cp_symbols", C.c_uint32), ("W", C.c_uint32), ("M", C.c_uint32),
                 ("thr", C.c_float), ("backoff", C.c_int32), ("first_start", C.c_int64)]
+
+
+class AcqParams(C.Structure):
+    """vit_acq_params of include/viterbi_amd.h: AcqParams(B, null_blocks, ref_blocks, period_blocks, thr, reserved, first,
+    offset)"""
+    _fields_ = [("B", C.c_uint32), ("null_blocks", C.c_uint32), ("ref_blocks", C.c_uint32), ("period_blocks", C.c_uint32),
+                ("thr", C.c_float), ("reserved", C.c_uint32), ("first", C.c_uint64), ("offset", C.c_int64)]
 
 
 # the four transmission modes of EN 300 401 as shapes (examples: the library compiles in no table of modes)
@@ -202,6 +209,7 @@ def lib():
         L.vit_ofdm_demap_soft_dev.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.POINTER(OfdmShape), ps, C.c_int64, vp, pr,
                                               C.c_uint64, vp, vp]
         L.vit_ofdm_demod_soft_dev.argtypes = [pi, pf, vp, C.POINTER(OfdmShape), ps, C.c_int64, vp, pr, C.c_uint64, vp, vp]
+        L.vit_ofdm_acquire_dev.argtypes = [vp, C.c_uint64, pf, C.POINTER(AcqParams), C.c_int64, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -786,6 +794,29 @@ def ofdm_sync_dev(d_iq, nfft, nsyms, nframes, d_tw, sym_stride, d_nco, nco_bits,
         return
     _check(lib().vit_ofdm_sync_dev(C.byref(inp), C.byref(par), _ptr(d_prs), nframes, _ptr(d_start_out), _ptr(d_rot_out),
                                    _ptr(d_info), _stream_ptr(stream)), "vit_ofdm_sync_dev")
+
+
+def ofdm_acquire_dev(d_iq, B, null_blocks, ref_blocks, period_blocks, thr, nperiods, d_start_out, first=0, offset=0,
+                     d_info=None, d_power=None, nsamples=None, stream=None, iq_format=IQ_F32, iq_scale=1.0):
+    """From the stream (include/viterbi_amd.h): the null-symbol search.  d_iq as iq_input (nsamples defaults to all of
+    it); per frame period of period_blocks blocks of B samples one coarse start into d_start_out (int64 CUDA tensor,
+    nperiods), the table ofdm_sync_dev takes as d_start; -1 where no edge passed thr.  d_info (optional): CUDA tensor of
+    4-byte elements, 4 words per period; d_power (optional): float32 CUDA tensor of (nsamples - first) // B block powers."""
+    total = _iq_samples(d_iq, iq_format)
+    n = total if nsamples is None else int(nsamples)
+    if n > total:
+        raise ValueError("d_iq must hold nsamples complex samples")
+    if not d_start_out.is_cuda or str(d_start_out.dtype) != "torch.int64" or d_start_out.numel() < nperiods:
+        raise ValueError("d_start_out must be an int64 CUDA tensor of nperiods elements")
+    if d_info is not None and (not d_info.is_cuda or d_info.element_size() != 4 or d_info.numel() < 4 * nperiods):
+        raise ValueError("d_info must be a CUDA tensor of 4*nperiods 4-byte elements")
+    nblk = max(n - int(first), 0) // int(B) if B else 0
+    if d_power is not None and (not d_power.is_cuda or str(d_power.dtype) != "torch.float32" or d_power.numel() < nblk):
+        raise ValueError("d_power must be a float32 CUDA tensor of (nsamples - first) // B elements")
+    par = AcqParams(int(B), int(null_blocks), int(ref_blocks), int(period_blocks), float(thr), 0, int(first), int(offset))
+    fmt = None if iq_format == IQ_F32 else C.byref(IqFormat(int(iq_format), float(iq_scale)))
+    _check(lib().vit_ofdm_acquire_dev(_ptr(d_iq), n, fmt, C.byref(par), nperiods, _ptr(d_start_out), _ptr(d_info),
+                                      _ptr(d_power), _stream_ptr(stream)), "vit_ofdm_acquire_dev")
 
 
 def decode_stream_multi(d_symbols_u8, d_out, framebits, nframes, devices, chunk_frames, root_frames=-1, flags=0,

@@ -1625,6 +1625,61 @@ int vit_iq_convert_dev(const void* d_iq, const vit_iq_format* fmt, uint64_t nsam
     return VIT_OK;
 }
 
+// ---- from the stream: first acquisition (vit_ofdm_acq.hip) ------------------------------------------------------------------
+int vit_ofdm_acquire_dev(const void* d_iq, uint64_t nsamples, const vit_iq_format* fmt, const vit_acq_params* p, int64_t nperiods,
+                         int64_t* d_start_out, uint32_t* d_info, float* d_power, void* stream) {
+    const char* who = "vit_ofdm_acquire_dev";
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (!fmt) fmt = &IQ_FORMAT_F32;
+    if (iq_check_format(who, fmt) != VIT_OK) return VIT_ERR_ARG;
+    if (!d_iq || !p || !d_start_out || nperiods < 0) {
+        set_err("%s: bad arguments (NULL d_iq, p or d_start_out, or nperiods=%lld < 0)", who, (long long)nperiods);
+        return VIT_ERR_ARG;
+    }
+    if (iq_check_alignment(who, d_iq, fmt) != VIT_OK) return VIT_ERR_ARG;
+    if (((uintptr_t)d_start_out & 7u) != 0 || ((uintptr_t)d_info & 3u) != 0 || ((uintptr_t)d_power & 3u) != 0) {
+        set_err("%s: bad arguments (d_start_out must be 8-byte aligned, d_info and d_power 4-byte aligned)", who);
+        return VIT_ERR_ARG;
+    }
+    if (p->B < 8u || p->B > 512u || (p->B & (p->B - 1u)) != 0 || p->null_blocks < 1u || p->null_blocks > 4096u ||
+        p->ref_blocks < 1u || p->ref_blocks > 4096u || p->period_blocks < 1u || !(p->thr > 0.0f && p->thr < __builtin_inff()) ||
+        p->reserved != 0u) {
+        set_err("%s: bad arguments (B=%u, a power of two 8 ... 512; null_blocks=%u and ref_blocks=%u, 1 ... 4096; period_blocks=%u "
+                ">= 1; thr=%g, finite and > 0; reserved=%u, 0)", who, p->B, p->null_blocks, p->ref_blocks, p->period_blocks,
+                (double)p->thr, p->reserved);
+        return VIT_ERR_ARG;
+    }
+    if (p->first > nsamples || nsamples > (UINT64_MAX >> 4)) {
+        set_err("%s: bad arguments (first=%llu <= nsamples=%llu < 2^60)", who, (unsigned long long)p->first,
+                (unsigned long long)nsamples);
+        return VIT_ERR_ARG;
+    }
+    if (nperiods == 0) return VIT_OK;
+    const uint64_t nblk = (nsamples - p->first) / p->B;
+    // the powers the search reads; a caller's d_power receives all of them
+    const unsigned __int128 reach = (unsigned __int128)(uint64_t)nperiods * p->period_blocks + p->null_blocks + p->ref_blocks - 1u;
+    const uint64_t npower = d_power || reach > (unsigned __int128)nblk ? nblk : (uint64_t)reach;
+    float* power = d_power;
+    const bool scratch = !d_power && npower > 0;
+    if (scratch) {
+        // the powers live in this thread's scratch ON THE CALLER'S CURRENT DEVICE; the buffer's reuse across the caller's
+        // streams is ordered by an event, like the u32 path's narrowing buffer
+        int dev = -1;
+        HIPCHK(hipGetDevice(&dev));
+        int rc = ctx_prepare(dev);
+        if (rc != VIT_OK) return rc;
+        if ((rc = grow_dev(&t_ctx.d_sym8, &t_ctx.d8_cap, (size_t)npower * sizeof(float))) != VIT_OK) return rc;
+        if (!t_ctx.scratch_ev) HIPCHK(hipEventCreateWithFlags(&t_ctx.scratch_ev, hipEventDisableTiming));
+        else HIPCHK(hipStreamWaitEvent((hipStream_t)stream, t_ctx.scratch_ev, 0));
+        power = (float*)t_ctx.d_sym8;
+    }
+    hipError_t e = vit_launch_acq_power(d_iq, *fmt, p->first, p->B, npower, power, (hipStream_t)stream);
+    if (e == hipSuccess) e = vit_launch_acq_search(power, nblk, *p, nperiods, d_start_out, d_info, (hipStream_t)stream);
+    if (e != hipSuccess) { set_err("acquisition launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
+    if (scratch) HIPCHK(hipEventRecord(t_ctx.scratch_ev, (hipStream_t)stream));
+    return VIT_OK;
+}
+
 void vit_sort_descs(vit_frame_desc* h_desc, int64_t nframes) {
     if (!h_desc || nframes <= 1) return;
     std::stable_sort(h_desc, h_desc + nframes,

@@ -112,6 +112,13 @@ hipError_t vit_launch_ofdm_demod(const vit_iq_input& in, const vit_iq_format& fm
 // From the coarse start (vit_ofdm_sync.hip): one workgroup per frame; the caller has checked every argument rule.
 hipError_t vit_launch_ofdm_sync(const vit_iq_input& in, const vit_iq_format& fmt, const vit_sync_params& p, const float* d_prs, int64_t nframes,
                                 int64_t* d_start_out, uint32_t* d_rot_out, uint32_t* d_info, hipStream_t stream);
+// From the stream (vit_ofdm_acq.hip); the caller has checked every argument rule.  The power of blocks 0 ... nblk-1 of B
+// samples behind sample `first` to d_power, then the search of nperiods periods on them (nblk: the blocks the stream
+// holds, which decide the candidates that exist - the search reads powers 0 ... min(nblk, Ln + nperiods*Pb + Lr - 1) - 1).
+hipError_t vit_launch_acq_power(const void* d_iq, const vit_iq_format& fmt, uint64_t first, uint32_t B, uint64_t nblk, float* d_power,
+                                hipStream_t stream);
+hipError_t vit_launch_acq_search(const float* d_power, uint64_t nblk, const vit_acq_params& p, int64_t nperiods, int64_t* d_start_out,
+                                 uint32_t* d_info, hipStream_t stream);
 // Integer samples to the floats of the definition (vit_iq_convert.hip): 2*nsamples floats to d_out; fmt is an integer
 // format, checked by the caller like the alignments.
 hipError_t vit_launch_iq_convert(const void* d_iq, const vit_iq_format& fmt, uint64_t nsamples, float* d_out, hipStream_t stream);
