@@ -673,6 +673,86 @@ int vit_ofdm_acquire_dev(const void *d_iq, uint64_t nsamples, const vit_iq_forma
                          int64_t *d_start_out, uint32_t *d_info /* optional, 4 words per period */,
                          float *d_power /* optional, nblk floats */, void *stream);
 
+/* Transmitter identification.  The null symbol of a transmission frame is silent except for a few carrier PAIRS per
+ * transmitter: the transmitter identification information (TII), which tells a receiver which transmitters of a
+ * single-frequency network it hears and how strongly.  The used carriers form R repetitions; a repetition has Gp groups
+ * of C pairs; a transmitter with main identifier p and sub identifier c switches on pair c in some of the Gp groups -
+ * which ones is the pattern of p - and does so identically in every repetition.  One call reads one window of nfft samples
+ * per frame - the null symbol - and writes, per group of navg frames, the noise level and per comb c a mask of the groups
+ * that stand out of it and their summed power: about 2 + 2C words, with no spectrum in memory.  The pair layout is a
+ * caller-supplied DEVICE table (like d_bins and d_prs: the device definition holds and needs no table of the standard);
+ * two host helpers below build the standard's tables for mode I.  Like the rest of the front end the result is defined bit
+ * for bit. */
+typedef struct vit_tii_params {
+    uint32_t nfft;      /* power of two 64 ... 8192 */
+    uint32_t ngroups;   /* Gp: groups per comb, 1 ... 32 (the standard: 8); a comb's mask is one uint32 */
+    uint32_t ncombs;    /* C: pairs per group, >= 1, Gp*C <= 1024 (the standard: 24) */
+    uint32_t nrep;      /* R: repetitions across the spectrum, 1 ... 8 (mode I: 4); 2*R*Gp*C <= nfft */
+    uint32_t navg;      /* frames summed into one estimate, 1 ... 256 */
+    float    thr;       /* a slot is "on" at thr times the noise level; finite, > 0 */
+    int64_t  offset;    /* the window starts at the frame's start + offset (mode I, start from vit_ofdm_sync_dev:
+                           -(int64_t)sym_stride, i.e. "symbol -1") */
+} vit_tii_params;
+/* Definition.  Every operation is one IEEE binary32 operation, rounded to nearest-even, in exactly this order, never
+ * contracted into an FMA; underflow is gradual, as in vit_ofdm_sync_dev.  in: the struct vit_ofdm_demod_dev takes - the
+ * same d_start table, and the d_rot table vit_ofdm_sync_dev wrote.  Gp, C, R, navg, thr, offset: the struct's.
+ * ngrp = ceil(nframes / navg); group g owns frames g*navg ... min((g+1)*navg, nframes) - 1.
+ * A. Window and spectrum.  Frame t with start s (in->d_start[t], or t*frame_stride) reads samples s + offset + i,
+ *    i = 0 ... nfft-1, components from the integer formats by the one-rounding rule of "Integer sample formats".  If
+ *    in->d_rot is given they are rotated by step 1 of "From the samples" with n = offset + i: n enters the phase modulo
+ *    2^32 as a two's-complement value, so the phase is the one the frame's own symbols continue.  X = the FFT of step 2
+ *    of it: the same graph, the same in->d_tw.
+ * B. Pair power.  For a table entry k = min(d_pairs[(r*Gp + b)*C + c], nfft-2) (clamped: no entry reads outside the symbol):
+ *      e = fl( fl(fl(X[k].re^2) + fl(X[k].im^2)) + fl(fl(X[k+1].re^2) + fl(X[k+1].im^2)) )
+ *    f_t[b][c] = the sum of e over r = 0 ... R-1 in ascending r, into ONE accumulator that starts at +0: acc = fl(acc + e).
+ * C. Group energy.  E_g[b][c] = the sum of f_t[b][c] over the group's frames in ascending t, in the same way, skipped
+ *    frames left out; nused = the number of frames that entered.
+ * D. Decision.  noise = the value of rank (Gp*C - 1) / 2 (integer division, 0-based, ascending) among the Gp*C values of
+ *    E_g: the lower median.  A selection rounds nothing, and ties do not change the value.
+ *      tau = fl(thr * noise)
+ *      bit b of mask[c] is set iff E_g[b][c] > 0 and E_g[b][c] >= tau
+ *      strength[c] = the sum of the E_g[b][c] whose bit is set, in ascending b, into one accumulator from +0
+ * E. Outputs.  d_tii[g*(2 + 2C) ...] = {uint32 nused, noise, mask[0], strength[0], ..., mask[C-1], strength[C-1]}, floats as
+ *    their bit patterns.  d_energy, if given, receives E_g[b][c] at (g*Gp + b)*C + c.  A group with nused = 0 gets zeros
+ *    throughout.  Nothing else is written; no sample outside the windows is read.
+ * The result depends on the samples, the tables and the struct alone: never on nframes beyond the group's own frames
+ * (group g has the same words in every call that holds all its frames), the launch or the device.
+ * Domain: the samples' domain of "From the samples" with magnitudes up to 2^12.  Then nothing overflows: the rotation
+ * keeps a magnitude (up to sqrt 2 per component), a spectrum component is a sum of nfft <= 2^13 such terms, at most
+ * 2^13 * 2^12 * sqrt 2 < 2^26; its square is under 2^52, e under 2^54, and the sums have at most R * navg = 8 * 256 terms
+ * (strength: Gp = 32 more): under 2^54 * 2^11 * 2^5 = 2^70.  tau = fl(thr * noise) may overflow to +Inf for a thr near
+ * FLT_MAX: then no bit is set.  All-zero windows are inside the domain: noise 0, every mask 0 (E > 0 fails).  Outside the
+ * domain the outputs of the groups that read such samples are unspecified; nothing but the call's output words is written.
+ * Skip rule: with in->d_start given, a frame with a negative start (the -1 of vit_ofdm_acquire_dev and
+ * vit_ofdm_sync_dev) is skipped, and so is a frame whose window is not inside [0, nsamples).  Without the table such a
+ * frame is VIT_ERR_ARG.
+ * Arguments as the other *_dev calls: VIT_ERR_NO_DEVICE first; VIT_ERR_ARG (with vit_last_error()) for a NULL in, p, d_iq,
+ * d_tw, d_pairs or d_tii; a d_iq that is not aligned as in "Integer sample formats" (8 bytes for float32, 4 for an integer
+ * format), a d_tw, d_nco, d_start or d_rot that is not 8-byte aligned, a d_pairs that is not 2-byte or a d_tii or d_energy
+ * that is not 4-byte aligned; every range in the struct's comments (thr NaN or Inf among them); d_rot without d_nco or with
+ * nco_bits outside 1 ... 20; the fmt rules of the *_iq_dev calls, except that a NULL fmt means float32; nframes < 0 or
+ * above 2^31 - 1.
+ * in->sym_stride is not read.  nframes = 0 returns VIT_OK and writes nothing.  The per-frame pair powers live in a buffer
+ * of the calling thread.  Everything is enqueued on `stream` without synchronising.
+ *
+ * The two host helpers hold what the standard's clause on TII says for mode I, as far as it is needed to use the call;
+ * the device definition depends on neither.  Both need no GPU.
+ *   vit_tii_pair_bins(1, h_pairs) writes the 768 entries of the d_pairs table for nfft = 2048, R = 4, Gp = 8, C = 24 and
+ *     returns 768: entry (r*8 + b)*24 + c is the FFT bin of carrier k0 = base[r] + 2c + 48b, base = {-768, -384, 1, 385},
+ *     a carrier k < 0 lying at bin 2048 + k; the pair is carriers k0 and k0 + 1.  Any other mode (II - IV were withdrawn
+ *     from the standard) or a NULL pointer returns -1.
+ *   vit_tii_main_id(mask): bit b of mask is group b, as in d_tii.  The standard's pattern word of a main identifier puts
+ *     group 0 in the MOST significant of its 8 bits; p is the rank of that word among the 70 eight-bit words with four
+ *     ones, in ascending numeric order: p = 0 is 0x0F, p = 1 is 0x17, ..., p = 69 is 0xF0.  So mask 0xF0 (groups 4 ... 7)
+ *     is p = 0.  Returns 0 ... 69, or -1 if the mask has not exactly four bits set or is above 255 (two transmitters
+ *     sharing a comb give the union of their patterns: the caller splits it by strength or over time). */
+int vit_ofdm_tii_dev(const vit_iq_input *in, const vit_iq_format *fmt /* NULL: float32 */, const vit_tii_params *p,
+                     const uint16_t *d_pairs /* DEVICE, R*Gp*C lower bins, index (r*Gp + b)*C + c */,
+                     int64_t nframes, uint32_t *d_tii /* ngrp * (2 + 2*C) words */,
+                     float *d_energy /* optional, ngrp * Gp*C floats */, void *stream);
+int64_t vit_tii_pair_bins(uint32_t mode, uint16_t *h_pairs);   /* host only: mode 1 -> 768 entries; else -1 */
+int     vit_tii_main_id(uint32_t mask);                        /* host only: 0 ... 69, or -1 if popcount != 4 or mask > 255 */
+
 /* Channel-state weighting: a second soft-decision rule.  The definition of vit_ofdm_demap_dev scales every carrier by its
  * own |re| + |im|, so a carrier in a fading notch reaches the decoder with the confidence of the strongest one.  The
  * per-symbol rule scales all K carriers of an OFDM symbol by one value, taken from the mean of |re| + |im| over the

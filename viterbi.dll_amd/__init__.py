@@ -34,6 +34,7 @@ EXPORTS = [
     "vit_fft_twiddles", "vit_nco_table", "vit_ofdm_fft_dev", "vit_ofdm_demod_dev", "vit_ofdm_sync_dev",
     "vit_ofdm_fft_iq_dev", "vit_ofdm_demod_iq_dev", "vit_ofdm_sync_iq_dev", "vit_iq_convert_dev",
     "vit_ofdm_demap_soft_dev", "vit_ofdm_demod_soft_dev", "vit_ofdm_acquire_dev",
+    "vit_ofdm_tii_dev", "vit_tii_pair_bins", "vit_tii_main_id",
     "vit_decode_stream_multi",
 ]
 MULTI_LOOPBACK = 0x1
@@ -117,6 +118,12 @@ class AcqParams(C.Structure):
     offset)"""
     _fields_ = [("B", C.c_uint32), ("null_blocks", C.c_uint32), ("ref_blocks", C.c_uint32), ("period_blocks", C.c_uint32),
                 ("thr", C.c_float), ("reserved", C.c_uint32), ("first", C.c_uint64), ("offset", C.c_int64)]
+
+
+class TiiParams(C.Structure):
+    """vit_tii_params of include/viterbi_amd.h: TiiParams(nfft, ngroups, ncombs, nrep, navg, thr, offset)"""
+    _fields_ = [("nfft", C.c_uint32), ("ngroups", C.c_uint32), ("ncombs", C.c_uint32), ("nrep", C.c_uint32),
+                ("navg", C.c_uint32), ("thr", C.c_float), ("offset", C.c_int64)]
 
 
 # the four transmission modes of EN 300 401 as shapes (examples: the library compiles in no table of modes)
@@ -210,6 +217,10 @@ def lib():
                                               C.c_uint64, vp, vp]
         L.vit_ofdm_demod_soft_dev.argtypes = [pi, pf, vp, C.POINTER(OfdmShape), ps, C.c_int64, vp, pr, C.c_uint64, vp, vp]
         L.vit_ofdm_acquire_dev.argtypes = [vp, C.c_uint64, pf, C.POINTER(AcqParams), C.c_int64, vp, vp, vp, vp]
+        L.vit_ofdm_tii_dev.argtypes = [pi, pf, C.POINTER(TiiParams), vp, C.c_int64, vp, vp, vp]
+        L.vit_tii_pair_bins.argtypes = [C.c_uint32, vp]
+        L.vit_tii_pair_bins.restype = C.c_int64
+        L.vit_tii_main_id.argtypes = [C.c_uint32]
         _lib = L
     return _lib
 
@@ -817,6 +828,61 @@ def ofdm_acquire_dev(d_iq, B, null_blocks, ref_blocks, period_blocks, thr, nperi
     fmt = None if iq_format == IQ_F32 else C.byref(IqFormat(int(iq_format), float(iq_scale)))
     _check(lib().vit_ofdm_acquire_dev(_ptr(d_iq), n, fmt, C.byref(par), nperiods, _ptr(d_start_out), _ptr(d_info),
                                       _ptr(d_power), _stream_ptr(stream)), "vit_ofdm_acquire_dev")
+
+
+def ofdm_tii_dev(d_iq, nfft, nframes, d_tw, d_pairs, d_tii, ngroups=8, ncombs=24, nrep=4, navg=8, thr=2.5, offset=0,
+                 d_start=None, frame_stride=None, d_nco=None, nco_bits=0, d_rot=None, d_energy=None, nsamples=None, stream=None,
+                 iq_format=IQ_F32, iq_scale=1.0):
+    """Transmitter identification (include/viterbi_amd.h): per frame the window of nfft samples at the frame's start +
+    offset - the null symbol; mode I behind ofdm_sync_dev: offset = -sym_stride -, per group of navg frames 2 + 2*ncombs
+    words into d_tii (CUDA tensor of 4-byte elements): {nused, noise, mask[0], strength[0], ...}, which tii_records views.
+    Input arguments as iq_input (d_start, or frame_stride, is required; d_rot is the table ofdm_sync_dev wrote); d_pairs:
+    CUDA tensor of 2-byte elements, nrep*ngroups*ncombs lower bins (tii_pair_bins(1) for mode I); d_energy (optional):
+    float32 CUDA tensor of ngrp*ngroups*ncombs group energies."""
+    if frame_stride is None and d_start is None:
+        raise ValueError("frame_stride or d_start is required")
+    slots = int(ngroups) * int(ncombs)
+    ngrp = -(-int(nframes) // int(navg)) if navg and nframes > 0 else 0
+    if not d_pairs.is_cuda or d_pairs.element_size() != 2 or d_pairs.numel() < int(nrep) * slots:
+        raise ValueError("d_pairs must be a CUDA tensor of nrep*ngroups*ncombs 2-byte elements (uint16 bins)")
+    if not d_tii.is_cuda or d_tii.element_size() != 4 or d_tii.numel() < ngrp * (2 + 2 * int(ncombs)):
+        raise ValueError("d_tii must be a CUDA tensor of ceil(nframes/navg) * (2 + 2*ncombs) 4-byte elements")
+    if d_energy is not None and (not d_energy.is_cuda or str(d_energy.dtype) != "torch.float32" or d_energy.numel() < ngrp * slots):
+        raise ValueError("d_energy must be a float32 CUDA tensor of ceil(nframes/navg) * ngroups*ncombs elements")
+    inp = iq_input(d_iq, d_tw, 0, frame_stride, d_start, d_nco, nco_bits, d_rot, nsamples, iq_format)
+    if inp.nsamples > _iq_samples(d_iq, iq_format):
+        raise ValueError("d_iq must hold nsamples complex samples")
+    par = TiiParams(int(nfft), int(ngroups), int(ncombs), int(nrep), int(navg), float(thr), int(offset))
+    fmt = None if iq_format == IQ_F32 else C.byref(IqFormat(int(iq_format), float(iq_scale)))
+    _check(lib().vit_ofdm_tii_dev(C.byref(inp), fmt, C.byref(par), _ptr(d_pairs), nframes, _ptr(d_tii), _ptr(d_energy),
+                                  _stream_ptr(stream)), "vit_ofdm_tii_dev")
+
+
+def tii_pair_bins(mode):
+    """the standard's TII carrier pairs as the d_pairs table of ofdm_tii_dev: uint16 numpy array (R, Gp, C) of lower FFT
+    bins - mode 1: (4, 8, 24) at nfft 2048; ValueError for any other mode (host only, needs no GPU)"""
+    out = np.zeros(768, np.uint16)
+    n = lib().vit_tii_pair_bins(int(mode) & 0xFFFFFFFF, _np(out))
+    if n != 768:
+        raise ValueError("only mode 1 has a TII table: %r" % (mode,))
+    return out.reshape(4, 8, 24)
+
+
+def tii_main_id(mask):
+    """a comb's mask (bit b = group b) -> the main identifier p, 0 ... 69, or -1 if it is no pattern of one transmitter
+    (not exactly four of the low 8 bits)"""
+    m = int(mask)
+    return -1 if m < 0 or m > 0xFFFFFFFF else int(lib().vit_tii_main_id(m))
+
+
+def tii_records(words, ncombs):
+    """a copied-back d_tii (numpy array of ngrp * (2 + 2*ncombs) 4-byte words) -> structured array (ngrp,) with the fields
+    nused (uint32), noise (float32), comb (ncombs,) of mask (uint32) and strength (float32); a view, nothing is copied"""
+    dt = np.dtype([("nused", "<u4"), ("noise", "<f4"), ("comb", [("mask", "<u4"), ("strength", "<f4")], (int(ncombs),))])
+    w = np.ascontiguousarray(words).reshape(-1)
+    if w.dtype.itemsize != 4 or w.size % (2 + 2 * int(ncombs)):
+        raise ValueError("words must hold whole records of 2 + 2*ncombs 4-byte words")
+    return w.view(dt)
 
 
 def decode_stream_multi(d_symbols_u8, d_out, framebits, nframes, devices, chunk_frames, root_frames=-1, flags=0,

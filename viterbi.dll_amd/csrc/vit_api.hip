@@ -1680,6 +1680,94 @@ int vit_ofdm_acquire_dev(const void* d_iq, uint64_t nsamples, const vit_iq_forma
     return VIT_OK;
 }
 
+// ---- transmitter identification from the null symbol (vit_ofdm_tii.hip) -------------------------------------------------------
+int vit_ofdm_tii_dev(const vit_iq_input* in, const vit_iq_format* fmt, const vit_tii_params* p, const uint16_t* d_pairs,
+                     int64_t nframes, uint32_t* d_tii, float* d_energy, void* stream) {
+    const char* who = "vit_ofdm_tii_dev";
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (!fmt) fmt = &IQ_FORMAT_F32;
+    if (iq_check_format(who, fmt) != VIT_OK) return VIT_ERR_ARG;
+    if (!in || !p || !d_pairs || !d_tii || !in->d_iq || !in->d_tw || nframes < 0) {
+        set_err("%s: bad arguments (NULL in, p, d_iq, d_tw, d_pairs or d_tii, or nframes=%lld < 0)", who, (long long)nframes);
+        return VIT_ERR_ARG;
+    }
+    if (iq_check_alignment(who, in->d_iq, fmt) != VIT_OK) return VIT_ERR_ARG;
+    if (((uintptr_t)in->d_tw & 7u) != 0 || ((uintptr_t)in->d_nco & 7u) != 0 || ((uintptr_t)in->d_start & 7u) != 0 ||
+        ((uintptr_t)in->d_rot & 7u) != 0 || ((uintptr_t)d_pairs & 1u) != 0 || ((uintptr_t)d_tii & 3u) != 0 ||
+        ((uintptr_t)d_energy & 3u) != 0) {
+        set_err("%s: bad arguments (d_tw, d_nco, d_start and d_rot must be 8-byte aligned, d_pairs 2-byte, d_tii and d_energy "
+                "4-byte aligned)", who);
+        return VIT_ERR_ARG;
+    }
+    if (in->d_rot && (!in->d_nco || in->nco_bits < 1u || in->nco_bits > 20u)) {
+        set_err("%s: bad arguments (d_rot needs d_nco and nco_bits 1 ... 20, got %u)", who, in->nco_bits);
+        return VIT_ERR_ARG;
+    }
+    if (p->nfft < 64u || p->nfft > 8192u || (p->nfft & (p->nfft - 1u)) != 0 || p->ngroups < 1u || p->ngroups > 32u ||
+        p->ncombs < 1u || (uint64_t)p->ngroups * p->ncombs > 1024u || p->nrep < 1u || p->nrep > 8u ||
+        2ull * p->nrep * p->ngroups * p->ncombs > p->nfft || p->navg < 1u || p->navg > 256u ||
+        !(p->thr > 0.0f && p->thr < __builtin_inff())) {
+        set_err("%s: bad arguments (nfft=%u, a power of two 64 ... 8192; ngroups=%u, 1 ... 32; ncombs=%u >= 1, ngroups*ncombs <= "
+                "1024; nrep=%u, 1 ... 8, 2*nrep*ngroups*ncombs <= nfft; navg=%u, 1 ... 256; thr=%g, finite and > 0)", who,
+                p->nfft, p->ngroups, p->ncombs, p->nrep, p->navg, (double)p->thr);
+        return VIT_ERR_ARG;
+    }
+    if (nframes > 0x7FFFFFFFll) {
+        set_err("%s: bad arguments (nframes=%lld, at most 2^31 - 1 per call)", who, (long long)nframes);
+        return VIT_ERR_ARG;
+    }
+    if (!in->d_start && nframes > 0) {
+        // the windows t*frame_stride + offset ... + nfft - 1: the first and the last bound all of them
+        const __int128 last = (__int128)((unsigned __int128)(uint64_t)(nframes - 1) * in->frame_stride);
+        if (p->offset < 0 || last > (__int128)INT64_MAX || last + p->offset + p->nfft > (__int128)in->nsamples ||
+            (__int128)p->offset + p->nfft > (__int128)in->nsamples) {
+            set_err("%s: bad arguments (%lld windows of %u samples at frame_stride %llu and offset %lld read outside [0, nsamples "
+                    "%llu))", who, (long long)nframes, p->nfft, (unsigned long long)in->frame_stride, (long long)p->offset,
+                    (unsigned long long)in->nsamples);
+            return VIT_ERR_ARG;
+        }
+    }
+    if (nframes == 0) return VIT_OK;
+    // the frames' pair powers live in this thread's scratch ON THE CALLER'S CURRENT DEVICE, ordered across the caller's
+    // streams by the event vit_ofdm_acquire_dev's powers use
+    int dev = -1;
+    HIPCHK(hipGetDevice(&dev));
+    int rc = ctx_prepare(dev);
+    if (rc != VIT_OK) return rc;
+    const size_t slots = (size_t)nframes * p->ngroups * p->ncombs * sizeof(float);
+    if ((rc = grow_dev(&t_ctx.d_sym8, &t_ctx.d8_cap, slots)) != VIT_OK) return rc;
+    if (!t_ctx.scratch_ev) HIPCHK(hipEventCreateWithFlags(&t_ctx.scratch_ev, hipEventDisableTiming));
+    else HIPCHK(hipStreamWaitEvent((hipStream_t)stream, t_ctx.scratch_ev, 0));
+    hipError_t e = vit_launch_ofdm_tii(*in, *fmt, *p, d_pairs, nframes, (float*)t_ctx.d_sym8, d_tii, d_energy, (hipStream_t)stream);
+    if (e != hipSuccess) { set_err("transmitter identification launch failed: %s", hipGetErrorString(e)); return VIT_ERR_HIP; }
+    HIPCHK(hipEventRecord(t_ctx.scratch_ev, (hipStream_t)stream));
+    return VIT_OK;
+}
+
+int64_t vit_tii_pair_bins(uint32_t mode, uint16_t* h_pairs) {
+    if (mode != 1u || !h_pairs) {
+        set_err("vit_tii_pair_bins: bad arguments (mode=%u: only mode 1 has a table; h_pairs non-NULL)", mode);
+        return -1;
+    }
+    static const int base[4] = {-768, -384, 1, 385};
+    for (int r = 0; r < 4; r++)
+        for (int b = 0; b < 8; b++)
+            for (int c = 0; c < 24; c++) {
+                const int k0 = base[r] + 2 * c + 48 * b;
+                h_pairs[(r * 8 + b) * 24 + c] = (uint16_t)(k0 < 0 ? 2048 + k0 : k0);
+            }
+    return 768;
+}
+
+int vit_tii_main_id(uint32_t mask) {
+    if (mask > 255u || __builtin_popcount(mask) != 4) return -1;
+    uint32_t word = 0;  // group 0 in the most significant of 8 bits
+    for (uint32_t b = 0; b < 8u; b++) word |= (mask >> b & 1u) << (7u - b);
+    int p = 0;
+    for (uint32_t w = 0; w < word; w++) p += __builtin_popcount(w) == 4;
+    return p;
+}
+
 void vit_sort_descs(vit_frame_desc* h_desc, int64_t nframes) {
     if (!h_desc || nframes <= 1) return;
     std::stable_sort(h_desc, h_desc + nframes,

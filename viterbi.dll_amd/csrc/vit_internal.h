@@ -119,6 +119,11 @@ hipError_t vit_launch_acq_power(const void* d_iq, const vit_iq_format& fmt, uint
                                 hipStream_t stream);
 hipError_t vit_launch_acq_search(const float* d_power, uint64_t nblk, const vit_acq_params& p, int64_t nperiods, int64_t* d_start_out,
                                  uint32_t* d_info, hipStream_t stream);
+// Transmitter identification (vit_ofdm_tii.hip); the caller has checked every argument rule.  One workgroup per frame
+// writes the frame's Gp*C pair powers to row t of d_slots (nframes rows; a skipped frame's row is neither written nor
+// read), then one workgroup per group of navg frames writes the group's words of d_tii and, if given, of d_energy.
+hipError_t vit_launch_ofdm_tii(const vit_iq_input& in, const vit_iq_format& fmt, const vit_tii_params& p, const uint16_t* d_pairs,
+                               int64_t nframes, float* d_slots, uint32_t* d_tii, float* d_energy, hipStream_t stream);
 // Integer samples to the floats of the definition (vit_iq_convert.hip): 2*nsamples floats to d_out; fmt is an integer
 // format, checked by the caller like the alignments.
 hipError_t vit_launch_iq_convert(const void* d_iq, const vit_iq_format& fmt, uint64_t nsamples, float* d_out, hipStream_t stream);
