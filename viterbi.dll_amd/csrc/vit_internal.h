@@ -1,4 +1,4 @@
-// vit_internal.h -- launchers shared between the kernel TUs and the C-ABI TU.
+// vit_internal.h -- launchers shared between the kernel TUs and the C-ABI TUs (whose own shared header is vit_host.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,7 +26,7 @@ hipError_t vit_launch_pk(const void* d_symbols, bool sym32, uint8_t* d_out, cons
                          uint32_t framebits, uint32_t max_framebits, int64_t nframes,
                          hipStream_t stream, bool renorm_ge);
 // Packed kernel, 8 frames per wavefront at 2 wavefronts per SIMD (vit_pk8.hip): frames of one segment (framebits <= 778).
-// An experiment, compiled in only with -DVIT_WITH_PK8 (otherwise vit_api.hip holds stubs that report "not supported").
+// An experiment, compiled in only with -DVIT_WITH_PK8 (otherwise vit_api_decode.hip holds stubs that report "not supported").
 bool vit_pk8_supported(uint32_t max_framebits);
 hipError_t vit_launch_pk8(const void* d_symbols, bool sym32, uint8_t* d_out, const vit_frame_desc* d_desc,
                           uint32_t framebits, uint32_t max_framebits, int64_t nframes, hipStream_t stream, bool renorm_ge);
@@ -37,7 +37,7 @@ hipError_t vit_launch_pk8(const void* d_symbols, bool sym32, uint8_t* d_out, con
 hipError_t vit_launch_lat(const void* d_symbols, bool sym32, uint8_t* d_out, const vit_frame_desc* d_desc,
                           uint32_t framebits, uint32_t max_framebits, int64_t nframes,
                           hipStream_t stream, uint32_t* done_flag, uint32_t done_seq, bool renorm_ge);
-// Ingest-stage launch (vit_api.hip): one frame per slot of a mapped pinned ring.  The table travels BY VALUE in the
+// Ingest-stage launch (vit_ring.hip): one frame per slot of a mapped pinned ring.  The table travels BY VALUE in the
 // kernel arguments (no descriptor fetch over PCIe in front of the symbol loads).
 #define VIT_RING_MAXB 128u  // frames per launch
 struct VitRingTable {

@@ -377,7 +377,7 @@ __global__ __launch_bounds__(64) void vit_lat_kernel(const uint8_t* __restrict__
         __hip_atomic_store(done_flag, done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// Ingest-stage launch (vit_api.hip): workgroup b decodes the frame a deconvolve() caller has put into
+// Ingest-stage launch (vit_ring.hip): workgroup b decodes the frame a deconvolve() caller has put into
 // slot tbl.slot[b] of the mapped pinned ring (symbols already narrowed to one byte each by the caller's copy) and
 // publishes the batch's sequence number in the slot's completion word after its last output byte, with system
 // scope - the caller spins on that word.  One bounded launch per batch, no polling on the device.

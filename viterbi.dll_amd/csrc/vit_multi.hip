@@ -312,10 +312,7 @@ int run(const uint8_t* d_sym, uint8_t* d_out, uint32_t framebits, int64_t nframe
 extern "C" int vit_decode_stream_multi(const uint8_t* d_symbols_u8, uint8_t* d_decoded, uint32_t framebits, int64_t nframes,
                                        const int* devices, int ndev, int64_t chunk_frames, int64_t root_frames,
                                        unsigned flags, void* stream) {
-    if (vit_device_count() <= 0) {
-        vit_set_err("no usable gfx950 (MI355X) HIP device; libviterbi has no CPU path");
-        return VIT_ERR_NO_DEVICE;
-    }
+    if (vit_device_count() <= 0) return VIT_ERR_NO_DEVICE;  // (the error text is the probe's: vit_device_count set it)
     const bool loopback = (flags & VIT_MULTI_LOOPBACK) != 0;
     const int W = ndev + (loopback ? 1 : 0);
     if (!devices || ndev < 1 || ndev > 64 || framebits > VIT_MAX_FRAMEBITS || (framebits & 1u) || nframes < 0 ||

@@ -3,7 +3,7 @@
 //
 // EN 300 401 clause 11 thins the K=7 rate-1/4 mother code by 32-bit puncturing vectors; a profile
 // (include/viterbi_amd.h: vit_punct_profile) writes them as per-segment period-8-step keep masks.  The expansion is a
-// separate pass in front of the unchanged decoders (vit_api.hip), like the u32 path's narrowing (vit_pack_kernel).
+// separate pass in front of the unchanged decoders (vit_api_decode.hip), like the u32 path's narrowing (vit_pack_kernel).
 //
 // One lane per trellis step writes that step's output dword, so a wavefront stores 256 contiguous bytes.  A step's
 // first transmitted byte is
