@@ -63,11 +63,7 @@ struct PrepassLane {
 };
 DEV PrepassLane prepass_lane(u32 lane) {
     PrepassLane p;
-#ifdef VIT_NO_PREPASS_SWAP  /* A/B: the round-3 store order (2-way bank conflict on both stores) */
-    const bool sw = false;
-#else
     const bool sw = (lane & 4u) != 0;
-#endif
     p.q0 = sw ? 0x03020302u : 0x01000100u;
     p.q1 = sw ? 0x01000100u : 0x03020302u;
     p.off0 = lane * 32u + (sw ? 16u : 0u);
