@@ -431,7 +431,8 @@ int vit_ofdm_demap_dev(const float *d_fft, uint64_t sym_stride, uint64_t frame_s
  * The two tables come from vit_ofdm_sync_dev ("From the coarse start", below) or from the caller's own estimator.
  * Integer samples as receivers deliver them go through the *_iq_dev calls ("Integer sample formats", below).
  * Channel-state weighting is a second soft-decision rule of both demappers ("Channel-state weighting", below).
- * First acquisition (finding the null symbol) is vit_ofdm_acquire_dev ("From the stream", below).  Out of scope: resampling. */
+ * First acquisition (finding the null symbol) is vit_ofdm_acquire_dev ("From the stream", below).  A stream at another
+ * sample rate, or one that holds several ensembles, goes through vit_iq_resample_dev first ("Before the stream", below). */
 typedef struct vit_iq_input {
     const float    *d_iq;         /* interleaved (re, im) float32 samples, 8-byte aligned (*_iq_dev: samples of fmt->format) */
     uint64_t        nsamples;     /* complex samples in d_iq: nothing at or beyond it is read */
@@ -613,6 +614,90 @@ int vit_ofdm_demod_iq_dev(const vit_iq_input *in, const vit_iq_format *fmt, cons
 int vit_ofdm_sync_iq_dev(const vit_iq_input *in, const vit_iq_format *fmt, const vit_sync_params *p, const float *d_prs,
                          int64_t nframes, int64_t *d_start_out, uint32_t *d_rot_out, uint32_t *d_info, void *stream);
 int vit_iq_convert_dev(const void *d_iq, const vit_iq_format *fmt, uint64_t nsamples, float *d_out, void *stream);
+
+/* Before the stream: rate conversion and channel selection.  Every stage from vit_ofdm_acquire_dev on takes a stream at
+ * the chain's sample rate (2.048 MS/s for DAB) that is centred on one ensemble.  Receivers deliver something else: an
+ * Airspy 2.5, 3, 6 or 10 MS/s, a USRP 2.0 or 2.5 MS/s, and a 6 or 10 MS/s capture covers three to five DAB blocks at once.
+ * One call shifts, low-pass filters and changes the rate by the rational factor L/M: it reads one stream - float32 or an
+ * integer format of "Integer sample formats", which is why the section stands behind it - once and writes nchan float32
+ * streams, each one ready for vit_ofdm_acquire_dev (d_out + 2*c*out_stride is channel c's d_iq).  It is a polyphase FIR
+ * filter with caller-supplied taps (the library holds no table of the standard; a host builder below gives
+ * windowed-sinc taps).  Like the rest of the front end the result is defined bit for bit. */
+#define VIT_RESAMPLE_MAX_CHAN 16
+typedef struct vit_resample_params {
+    uint32_t L, M;        /* output rate = input rate * L / M; 1 <= L <= 1024, 1 <= M <= 4096 (need not be coprime) */
+    uint32_t T;           /* taps per phase: a multiple of 4, 4 ... 128; L*T <= 16384 */
+    uint32_t nchan;       /* 1 ... VIT_RESAMPLE_MAX_CHAN */
+    uint64_t pos0;        /* position of output 0 in units of 1/L input sample (stream continuation, below) */
+    const float *d_taps;  /* DEVICE: L*T floats, phase-major g[phi*T + k], from vit_resample_taps or the caller's own */
+    const float *d_nco;   /* DEVICE: 2^nco_bits phasors from vit_nco_table; required iff rot != NULL */
+    uint32_t nco_bits;    /* 1 ... 20 (read only when rot is given) */
+    uint32_t reserved;    /* 0 */
+    const uint32_t *rot;  /* HOST, read during the call: nchan pairs {phase0, step}; NULL = no rotation, nchan must be 1 */
+} vit_resample_params;
+/* Definition.  Every operation is one IEEE binary32 operation, rounded to nearest-even, in exactly this order, never
+ * contracted into an FMA.  L, M, T, nchan, pos0, rot: the struct's; g = d_taps, nco = d_nco.
+ * A. Sample.  x[n], n = 0 ... nsamples-1, is sample n of d_iq as binary32: the value itself for float32, components from
+ *    the integer formats by the one-rounding rule of "Integer sample formats".
+ * B. Rotation, channel c, only if rot is given.  With {phase0, step} = rot[2c], rot[2c+1] and n the index into d_iq, of
+ *    which only the low 32 bits matter:
+ *      w = nco[((phase0 + n*step) mod 2^32) >> (32 - nco_bits)]
+ *      y.re = fl(fl(x.re*w.re) - fl(x.im*w.im))
+ *      y.im = fl(fl(x.re*w.im) + fl(x.im*w.re))
+ *    the graph of step 1 of "From the samples"; step = round(-f/fs * 2^32) mod 2^32 moves a channel centred at f, at input
+ *    rate fs, to 0.  Without rot, y = x: no rotation, not even by 1.
+ * C. Filter.  Output m, 0 <= m < nout, has P = pos0 + m*M in 64-bit arithmetic, n0 = P div L, phi = P mod L.  For each of
+ *    the two components:
+ *      term[k] = fl(g[phi*T + k] * y[n0 + k]),  k = 0 ... T-1
+ *      four accumulators a0 ... a3 start at +0; in ascending k, term[k] is added to accumulator k mod 4: a = fl(a + term[k])
+ *      result = fl( fl(a0 + a1) + fl(a2 + a3) )
+ *    It is written to complex element c*out_stride + m of d_out (floats 2*(c*out_stride + m) and the next).  Results are
+ *    defined by value (-0 = +0).
+ * D. Reads and writes.  Output m reads samples n0 ... n0 + T - 1 and nothing else: no sample at or beyond nsamples is read,
+ *    and none that no requested output needs - not in front of the first output's n0, not behind the last one's
+ *    n0 + T - 1, not in a gap between two outputs' samples (M > L*T).  Only the nchan*nout named complex elements of d_out
+ *    are written: not the gaps between channels when out_stride > nout.
+ * The result depends on the samples, the tables and the struct alone: never on nout (output m has the same bits in every
+ * call that reaches it), never on nchan (channel c has the same bits alone, with nchan = 1 and its own pair, or among
+ * others), never on the launch or the device.
+ * Stream continuation.  A caller who has consumed outputs 0 ... m1-1 and drops the first s = (pos0 + m1*M) div L samples of
+ * the buffer (any s up to that; this is the most) calls again with
+ *      pos0'   = (pos0 + m1*M) - s*L
+ *      phase0' = (phase0 + s*step) mod 2^32     for every channel
+ * on the buffer that starts at the old sample s: output m of the second call equals, bit for bit, output m1 + m of one long
+ * call.  (n0 and n move by s together; phi, and the phase of every sample, stay.)
+ * Timing.  Output m sits at input time (pos0 + m*M)/L + d, d the delay of the taps; the taps of vit_resample_taps have
+ * d = T/2 - 1 input samples at every phase, a constant the caller adds to its start tables (in output samples: d*L/M).
+ * Domain: every component of a sample is 0 or has a magnitude in [2^-40, 2^12] - the domain of vit_ofdm_acquire_dev and
+ * vit_ofdm_sync_dev, which read the output; the taps are finite with |g| <= 4.  Then nothing overflows: a rotated
+ * component is under 2^13, a term under 2^15, an accumulator under 32 * 2^15 and the result under 2^22.  Underflow is
+ * gradual: denormal products and sums are kept as IEEE arithmetic has them, as in step A of vit_ofdm_sync_dev.  All-zero
+ * samples are inside the domain and give zeros.  Outside the domain the outputs that read such samples are unspecified;
+ * nothing but the named output words is written.
+ * Host helpers, no GPU (like vit_fft_twiddles):
+ *   vit_resample_out_count(nsamples, p): the largest nout for which the last output's n0 + T <= nsamples (and its P fits 64
+ *     bits), clamped to 2^63 - 1; 0 if there is none (nsamples < T among the reasons); -1 for a NULL pointer or L, M, T
+ *     outside their ranges.  It reads L, M, T and pos0 only.
+ *   vit_resample_taps(L, T, cutoff, h_taps): a Blackman-windowed sinc, computed in binary64 and rounded to binary32.  For
+ *     phase phi and tap k, with u = k - (T/2 - 1) - phi/L and sinc(x) = sin(pi x)/(pi x), sinc(0) = 1:
+ *       h = 2*cutoff * sinc(2*cutoff*u) * (0.42 + 0.5 cos(2 pi u / T) + 0.08 cos(4 pi u / T))
+ *     Each phase's T values are divided by their binary64 sum (ascending k), so the gain at DC is 1 at every phase, and
+ *     then rounded.  cutoff is in cycles per INPUT sample, 0 < cutoff <= 0.5: when the rate goes down it must lie
+ *     under half the OUTPUT rate, L/(2M).  Returns L*T, or -1 for a NULL pointer or an argument out of range (L, T as in
+ *     the struct).
+ * Arguments as the other *_dev calls: VIT_ERR_NO_DEVICE first; VIT_ERR_ARG (with vit_last_error()) for a NULL d_iq, p,
+ * d_taps or d_out; a d_iq that is not aligned as in "Integer sample formats" (8 bytes for float32, 4 for an integer
+ * format); a d_taps, d_nco or d_out that is not 8-byte aligned; every range in the struct's comments; a nonzero reserved;
+ * rot without d_nco, d_nco without rot, rot == NULL with nchan > 1; the fmt rules of vit_ofdm_acquire_dev (an unknown
+ * format, a scale outside its range; a NULL fmt means float32); nsamples >= 2^60; nout < 0 or nout >
+ * vit_resample_out_count(nsamples, p); nchan > 1 with out_stride < nout.  Sample positions stay arbitrary: a CU8 output's
+ * first sample may lie at an address that is 2 mod 4.  nout = 0 returns VIT_OK and writes nothing.  Everything is enqueued
+ * on `stream` without synchronising; the call needs no buffer of the calling thread. */
+int64_t vit_resample_taps(uint32_t L, uint32_t T, double cutoff, float *h_taps);
+int64_t vit_resample_out_count(uint64_t nsamples, const vit_resample_params *p);
+int vit_iq_resample_dev(const void *d_iq, uint64_t nsamples, const vit_iq_format *fmt /* NULL: float32 */,
+                        const vit_resample_params *p, int64_t nout,
+                        float *d_out, uint64_t out_stride /* complex samples between channels */, void *stream);
 
 /* From the stream: first acquisition.  What a receiver does first: it has an unaligned stream of samples and must find
  * where the frames start.  One call searches one contiguous stream - float32, or an integer format of "Integer sample

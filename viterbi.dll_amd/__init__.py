@@ -35,6 +35,7 @@ EXPORTS = [
     "vit_ofdm_fft_iq_dev", "vit_ofdm_demod_iq_dev", "vit_ofdm_sync_iq_dev", "vit_iq_convert_dev",
     "vit_ofdm_demap_soft_dev", "vit_ofdm_demod_soft_dev", "vit_ofdm_acquire_dev",
     "vit_ofdm_tii_dev", "vit_tii_pair_bins", "vit_tii_main_id",
+    "vit_resample_taps", "vit_resample_out_count", "vit_iq_resample_dev",
     "vit_decode_stream_multi",
 ]
 MULTI_LOOPBACK = 0x1
@@ -125,6 +126,16 @@ class TiiParams(C.Structure):
     _fields_ = [("nfft", C.c_uint32), ("ngroups", C.c_uint32), ("ncombs", C.c_uint32), ("nrep", C.c_uint32),
                 ("navg", C.c_uint32), ("thr", C.c_float), ("offset", C.c_int64)]
 
+
+class ResampleParams(C.Structure):
+    """vit_resample_params of include/viterbi_amd.h: ResampleParams(L, M, T, nchan, pos0, d_taps, d_nco, nco_bits, reserved,
+    rot)"""
+    _fields_ = [("L", C.c_uint32), ("M", C.c_uint32), ("T", C.c_uint32), ("nchan", C.c_uint32), ("pos0", C.c_uint64),
+                ("d_taps", C.c_void_p), ("d_nco", C.c_void_p), ("nco_bits", C.c_uint32), ("reserved", C.c_uint32),
+                ("rot", C.c_void_p)]
+
+
+RESAMPLE_MAX_CHAN = 16
 
 # the four transmission modes of EN 300 401 as shapes (examples: the library compiles in no table of modes)
 OFDM_MODES = {1: (2048, 1536, 76, 3, 4), 2: (512, 384, 76, 3, 1), 3: (256, 192, 153, 8, 1), 4: (1024, 768, 76, 3, 2)}
@@ -221,6 +232,11 @@ def lib():
         L.vit_tii_pair_bins.argtypes = [C.c_uint32, vp]
         L.vit_tii_pair_bins.restype = C.c_int64
         L.vit_tii_main_id.argtypes = [C.c_uint32]
+        L.vit_resample_taps.argtypes = [C.c_uint32, C.c_uint32, C.c_double, vp]
+        L.vit_resample_taps.restype = C.c_int64
+        L.vit_resample_out_count.argtypes = [C.c_uint64, C.POINTER(ResampleParams)]
+        L.vit_resample_out_count.restype = C.c_int64
+        L.vit_iq_resample_dev.argtypes = [vp, C.c_uint64, pf, C.POINTER(ResampleParams), C.c_int64, vp, C.c_uint64, vp]
         _lib = L
     return _lib
 
@@ -828,6 +844,73 @@ def ofdm_acquire_dev(d_iq, B, null_blocks, ref_blocks, period_blocks, thr, nperi
     fmt = None if iq_format == IQ_F32 else C.byref(IqFormat(int(iq_format), float(iq_scale)))
     _check(lib().vit_ofdm_acquire_dev(_ptr(d_iq), n, fmt, C.byref(par), nperiods, _ptr(d_start_out), _ptr(d_info),
                                       _ptr(d_power), _stream_ptr(stream)), "vit_ofdm_acquire_dev")
+
+
+def resample_taps(L, T, cutoff):
+    """Before the stream (include/viterbi_amd.h): the Blackman-windowed sinc of vit_resample_taps, cutoff in cycles per
+    input sample -> float32 numpy array (L, T), row phi the taps of phase phi; ValueError for an argument out of range
+    (host only, needs no GPU)"""
+    if not (1 <= int(L) <= 1024 and 4 <= int(T) <= 128):
+        raise ValueError("L must be 1 ... 1024 and T a multiple of 4, 4 ... 128: %r, %r" % (L, T))
+    out = np.zeros((int(L), int(T)), np.float32)
+    if lib().vit_resample_taps(int(L), int(T), float(cutoff), _np(out)) != out.size:
+        raise ValueError("L*T must be <= 16384, T a multiple of 4 and 0 < cutoff <= 0.5: %r, %r, %r" % (L, T, cutoff))
+    return out
+
+
+def resample_out_count(nsamples, L, M, T, pos0=0):
+    """the most outputs vit_iq_resample_dev forms from nsamples samples (host only, needs no GPU); ValueError for L, M or
+    T out of range"""
+    for v in (nsamples, L, M, T, pos0):
+        if int(v) < 0:
+            raise ValueError("nsamples, L, M, T and pos0 must not be negative")
+    par = ResampleParams(int(L) & 0xFFFFFFFF, int(M) & 0xFFFFFFFF, int(T) & 0xFFFFFFFF, 1, int(pos0), None, None, 0, 0, None)
+    n = lib().vit_resample_out_count(int(nsamples), C.byref(par))
+    if n < 0:
+        raise ValueError("L must be 1 ... 1024, M 1 ... 4096, T a multiple of 4, 4 ... 128, L*T <= 16384: %r, %r, %r" % (L, M, T))
+    return n
+
+
+def resample_tile(L, M, T):
+    """-> (outputs one workgroup of vit_iq_resample_dev forms, whether its threads read their samples from memory): the
+    rule of csrc/vit_resample.hip (resample_tile there), restated for the tests that place nout around a tile's edge"""
+    if M > L * T:
+        return 512, True
+    tile = 1024
+    while tile > 1 and ((tile - 1) * M + L - 1) // L + T > 2048:
+        tile //= 2
+    return tile, False
+
+
+def iq_resample_dev(d_iq, L, M, d_taps, nout, d_out, pos0=0, rot=None, d_nco=None, nco_bits=0, out_stride=None, nsamples=None,
+                    stream=None, iq_format=IQ_F32, iq_scale=1.0):
+    """Before the stream (include/viterbi_amd.h): frequency shift, low-pass and rate change by L/M.  d_iq as iq_input
+    (nsamples defaults to all of it); d_taps: float32 CUDA tensor (L, T) from resample_taps; rot: None, or nchan pairs
+    (phase0, step) - a sequence or a numpy array, read during the call - with d_nco, a float32 CUDA tensor from nco_table,
+    and its nco_bits; d_out: complex64 or float32 CUDA tensor, channel c's nout outputs from complex element c*out_stride
+    on (out_stride defaults to nout)."""
+    total = _iq_samples(d_iq, iq_format)
+    n = total if nsamples is None else int(nsamples)
+    if n > total:
+        raise ValueError("d_iq must hold nsamples complex samples")
+    if not d_taps.is_cuda or str(d_taps.dtype) != "torch.float32" or d_taps.dim() != 2 or d_taps.shape[0] != int(L) or \
+            not d_taps.is_contiguous():
+        raise ValueError("d_taps must be a contiguous float32 CUDA tensor (L, T)")
+    if d_nco is not None and (not d_nco.is_cuda or str(d_nco.dtype) != "torch.float32"):
+        raise ValueError("d_nco must be a float32 CUDA tensor")
+    if not d_out.is_cuda or str(d_out.dtype) not in ("torch.complex64", "torch.float32"):
+        raise ValueError("d_out must be a complex64 or float32 CUDA tensor")
+    pairs = None if rot is None else np.ascontiguousarray(np.asarray(rot, np.int64).reshape(-1, 2) & 0xFFFFFFFF, np.uint32)
+    nchan = 1 if pairs is None else pairs.shape[0]
+    stride = int(nout) if out_stride is None else int(out_stride)
+    if nout < 0 or stride < 0 or d_out.numel() * d_out.element_size() < 8 * ((nchan - 1) * stride + nout):
+        raise ValueError("d_out must hold nchan channels of nout complex samples at out_stride")
+    par = ResampleParams(int(L), int(M), int(d_taps.shape[1]), nchan, int(pos0), d_taps.data_ptr(),
+                         None if d_nco is None else d_nco.data_ptr(), int(nco_bits), 0,
+                         None if pairs is None else pairs.ctypes.data)
+    fmt = None if iq_format == IQ_F32 else C.byref(IqFormat(int(iq_format), float(iq_scale)))
+    _check(lib().vit_iq_resample_dev(_ptr(d_iq), n, fmt, C.byref(par), int(nout), _ptr(d_out), stride, _stream_ptr(stream)),
+           "vit_iq_resample_dev")
 
 
 def ofdm_tii_dev(d_iq, nfft, nframes, d_tw, d_pairs, d_tii, ngroups=8, ncombs=24, nrep=4, navg=8, thr=2.5, offset=0,

@@ -1,7 +1,8 @@
 // vit_api_ofdm.hip -- the C ABI of the receiver front (include/viterbi_amd.h): bins, twiddles and the NCO table, demapping,
-// FFT and demodulation, fine synchronisation, sample conversion, first acquisition and transmitter identification.
-// Argument rules and launches only: vit_host.h has what the units of the C ABI share.
+// FFT and demodulation, fine synchronisation, sample conversion, rate conversion, first acquisition and transmitter
+// identification.  Argument rules and launches only: vit_host.h has what the units of the C ABI share.
 #include <climits>
+#include <cmath>
 
 #include "vit_host.h"
 
@@ -290,6 +291,83 @@ int vit_iq_convert_dev(const void* d_iq, const vit_iq_format* fmt, uint64_t nsam
                        who, (unsigned long long)nsamples);
     if (nsamples == 0) return VIT_OK;
     LAUNCHCHK("sample conversion launch failed: %s", vit_launch_iq_convert(d_iq, *fmt, nsamples, d_out, (hipStream_t)stream));
+    return VIT_OK;
+}
+
+// ---- before the stream: rate conversion and channel selection (vit_resample.hip) ---------------------------------------------
+int64_t vit_resample_taps(uint32_t L, uint32_t T, double cutoff, float* h_taps) {
+    if (!h_taps || L < 1u || L > 1024u || T < 4u || T > 128u || (T & 3u) != 0 || L * T > 16384u || !(cutoff > 0.0 && cutoff <= 0.5)) {
+        set_err("vit_resample_taps: bad arguments (L=%u, 1 ... 1024; T=%u, a multiple of 4, 4 ... 128; L*T <= 16384; cutoff=%g, 0 < "
+                "cutoff <= 0.5; h_taps non-NULL)", L, T, cutoff);
+        return -1;
+    }
+    const double pi = 3.14159265358979323846;
+    double h[128];
+    for (uint32_t phi = 0; phi < L; phi++) {
+        double sum = 0.0;
+        for (uint32_t k = 0; k < T; k++) {
+            const double u = (double)k - (double)(T / 2u - 1u) - (double)phi / (double)L;
+            const double x = 2.0 * cutoff * u;
+            const double sinc = x == 0.0 ? 1.0 : sin(pi * x) / (pi * x);
+            h[k] = 2.0 * cutoff * sinc * (0.42 + 0.5 * cos(2.0 * pi * u / T) + 0.08 * cos(4.0 * pi * u / T));
+            sum += h[k];
+        }
+        for (uint32_t k = 0; k < T; k++) h_taps[(size_t)phi * T + k] = (float)(h[k] / sum);
+    }
+    return (int64_t)L * T;
+}
+
+// the ranges of L, M and T: what the positions of the outputs depend on
+static bool resample_ratio_ok(const vit_resample_params* p) {
+    return p->L >= 1u && p->L <= 1024u && p->M >= 1u && p->M <= 4096u && p->T >= 4u && p->T <= 128u && (p->T & 3u) == 0 &&
+           p->L * p->T <= 16384u;
+}
+static int64_t resample_out_count(uint64_t nsamples, const vit_resample_params* p) {
+    if (nsamples < p->T) return 0;
+    // the last output's P <= (nsamples - T + 1)*L - 1, and P stays inside 64 bits
+    unsigned __int128 pmax = (unsigned __int128)(nsamples - p->T + 1u) * p->L - 1u;
+    if (pmax > (unsigned __int128)UINT64_MAX) pmax = UINT64_MAX;
+    if ((unsigned __int128)p->pos0 > pmax) return 0;
+    const unsigned __int128 n = (pmax - p->pos0) / p->M + 1u;
+    return n > (unsigned __int128)INT64_MAX ? INT64_MAX : (int64_t)n;
+}
+
+int64_t vit_resample_out_count(uint64_t nsamples, const vit_resample_params* p) {
+    if (!p || !resample_ratio_ok(p)) {
+        set_err("vit_resample_out_count: bad arguments (NULL p, or L 1 ... 1024, M 1 ... 4096, T a multiple of 4, 4 ... 128, L*T <= 16384)");
+        return -1;
+    }
+    return resample_out_count(nsamples, p);
+}
+
+int vit_iq_resample_dev(const void* d_iq, uint64_t nsamples, const vit_iq_format* fmt, const vit_resample_params* p, int64_t nout,
+                        float* d_out, uint64_t out_stride, void* stream) {
+    const char* who = "vit_iq_resample_dev";
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    if (!fmt) fmt = &IQ_FORMAT_F32;
+    if (iq_check_format(who, fmt) != VIT_OK) return VIT_ERR_ARG;
+    if (!d_iq || !p || !p->d_taps || !d_out || nout < 0)
+        return bad_arg("%s: bad arguments (NULL d_iq, p, d_taps or d_out, or nout=%lld < 0)", who, (long long)nout);
+    if (iq_check_alignment(who, d_iq, fmt) != VIT_OK) return VIT_ERR_ARG;
+    if ((((uintptr_t)p->d_taps | (uintptr_t)p->d_nco | (uintptr_t)d_out) & 7u) != 0)
+        return bad_arg("%s: bad arguments (d_taps, d_nco and d_out must be 8-byte aligned)", who);
+    if (!resample_ratio_ok(p) || p->nchan < 1u || p->nchan > VIT_RESAMPLE_MAX_CHAN || p->reserved != 0u)
+        return bad_arg("%s: bad arguments (L=%u, 1 ... 1024; M=%u, 1 ... 4096; T=%u, a multiple of 4, 4 ... 128; L*T <= 16384; nchan=%u, "
+                       "1 ... %u; reserved=%u, 0)", who, p->L, p->M, p->T, p->nchan, (unsigned)VIT_RESAMPLE_MAX_CHAN, p->reserved);
+    if ((p->rot != nullptr) != (p->d_nco != nullptr) || (!p->rot && p->nchan > 1u) ||
+        (p->rot && (p->nco_bits < 1u || p->nco_bits > 20u)))
+        return bad_arg("%s: bad arguments (rot and d_nco go together, with nco_bits 1 ... 20, got %u; without them nchan=%u must be 1)",
+                       who, p->nco_bits, p->nchan);
+    if (nsamples > (UINT64_MAX >> 4)) return bad_arg("%s: bad arguments (nsamples=%llu >= 2^60)", who, (unsigned long long)nsamples);
+    const int64_t most = resample_out_count(nsamples, p);
+    if (nout > most)
+        return bad_arg("%s: bad arguments (nout=%lld: %llu samples from pos0=%llu hold %lld outputs)", who, (long long)nout,
+                       (unsigned long long)nsamples, (unsigned long long)p->pos0, (long long)most);
+    if (p->nchan > 1u && out_stride < (uint64_t)nout)
+        return bad_arg("%s: bad arguments (out_stride=%llu < nout=%lld with %u channels)", who, (unsigned long long)out_stride,
+                       (long long)nout, p->nchan);
+    if (nout == 0) return VIT_OK;
+    LAUNCHCHK("resampler launch failed: %s", vit_launch_resample(d_iq, *fmt, *p, nout, d_out, out_stride, (hipStream_t)stream));
     return VIT_OK;
 }
 

@@ -119,6 +119,10 @@ hipError_t vit_launch_acq_power(const void* d_iq, const vit_iq_format& fmt, uint
                                 hipStream_t stream);
 hipError_t vit_launch_acq_search(const float* d_power, uint64_t nblk, const vit_acq_params& p, int64_t nperiods, int64_t* d_start_out,
                                  uint32_t* d_info, hipStream_t stream);
+// Before the stream (vit_resample.hip); the caller has checked every argument rule, nout <= vit_resample_out_count among
+// them.  fmt as above; p.rot is read during the call (it travels in the kernel arguments).
+hipError_t vit_launch_resample(const void* d_iq, const vit_iq_format& fmt, const vit_resample_params& p, int64_t nout, float* d_out,
+                               uint64_t out_stride, hipStream_t stream);
 // Transmitter identification (vit_ofdm_tii.hip); the caller has checked every argument rule.  One workgroup per frame
 // writes the frame's Gp*C pair powers to row t of d_slots (nframes rows; a skipped frame's row is neither written nor
 // read), then one workgroup per group of navg frames writes the group's words of d_tii and, if given, of d_energy.
