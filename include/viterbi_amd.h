@@ -359,6 +359,85 @@ int vit_dabplus_ti_superframes_dev(const vit_cif_ring *ring, uint64_t col, const
                                    uint8_t erasure, uint8_t *d_work, uint8_t *d_rs_out, int32_t *d_ret,
                                    uint8_t *d_fire_ok, uint32_t RSDims, int64_t nsf, void *stream);
 
+/* A whole ensemble: every sub-channel of the MSC in one table-driven chain.  The calls above take one sub-channel; a
+ * multiplex carries a dozen or more DAB+ services of different sizes whose superframes start at different CIF phases,
+ * and often a data or DAB audio sub-channel beside them.  The table below names them all, and each call here is a
+ * fixed number of launches whatever the table's length.
+ * The table is a HOST array, read during the call like `profile` of the uniform calls (it travels in the kernel
+ * arguments; nothing is uploaded).  Entry k:
+ *   DAB+ (RSDims 1 ... 48)   nframes/5 superframes of five logical frames of framebits = 192*RSDims bits; decoded,
+ *                            descrambled, fire code, RS, access units
+ *   not DAB+ (RSDims 0)      nframes logical frames of framebits bits (a multiple of 8): decoded and descrambled only
+ * Layout rule (vit_ensemble_layout computes it; it is fixed):
+ *   - sub-channels come in table order;
+ *   - in d_work, sub-channel k's decoded and descrambled frames lie back to back at framebits/8 bytes each from
+ *     work_offset[k] (DAB+: five frames are one RS input block of 120*RSDims bytes, as in the chains above);
+ *   - in d_rs_out, its superframes lie back to back at 110*RSDims bytes each from rs_offset[k]; a sub-channel that is
+ *     not DAB+ takes nothing there;
+ *   - every sub-channel's block starts at the next multiple of 16 bytes behind the previous one's end (the first at 0);
+ *     work_bytes / rs_bytes are the end of the last block;
+ *   - d_ret, d_fire_ok and d_au hold one record per superframe in table order, DAB+ sub-channels only: sub-channel k's
+ *     superframe s is record rec_index[k] + s (rec_index of an entry that is not DAB+ is the next DAB+ entry's).
+ * vit_ensemble_layout needs no GPU.  It returns VIT_ERR_ARG, with vit_last_error() naming the entry, for nsub outside
+ * 1 ... VIT_ENS_MAX_SUBCH, a framebits that is 0, above 9216 or no multiple of 8, RSDims > 48, a DAB+ entry whose
+ * framebits is not 192*RSDims or whose nframes is no multiple of 5, nframes = 0, phase + nframes + 15 beyond 32 bits,
+ * or a non-zero reserved field.  Every device entry point below runs the same validation first. */
+#define VIT_ENS_MAX_SUBCH 64
+typedef struct vit_ens_subch {   /* 32 bytes */
+    uint32_t col;        /* column of its first transmitted symbol, relative to msc_col (64 * start CU) */
+    uint32_t profile;    /* index into d_profiles */
+    uint32_t framebits;  /* per logical frame: a multiple of 8, 8 ... 9216; DAB+: exactly 192*RSDims */
+    uint32_t RSDims;     /* 0: not DAB+ (decode + descramble only); 1 ... 48: DAB+ */
+    uint32_t phase;      /* logical frame of the call at which this sub-channel starts (DAB+: a superframe start) */
+    uint32_t nframes;    /* logical frames to process, >= 1; DAB+: a multiple of 5 */
+    uint32_t nsym;       /* transmitted symbols per frame = vit_punctured_length(its profile, framebits) */
+    uint32_t reserved;   /* 0 */
+} vit_ens_subch;
+typedef struct vit_ens_layout {
+    uint64_t work_offset[VIT_ENS_MAX_SUBCH], rs_offset[VIT_ENS_MAX_SUBCH], rec_index[VIT_ENS_MAX_SUBCH];
+    uint64_t work_bytes, rs_bytes, nrec;    /* sizes of d_work, d_rs_out; records in d_ret / d_fire_ok / d_au */
+    uint32_t rows_needed, max_framebits;    /* max(phase + nframes) + 15; largest framebits */
+} vit_ens_layout;
+int vit_ensemble_layout(const vit_ens_subch *h_sub, uint32_t nsub, vit_ens_layout *h_out);
+/* Table forms of the stages after the decoder, ONE launch each over all DAB+ sub-channels of the table (entries that
+ * are not DAB+ are passed over; col, profile, phase and nsym are not used).  Per superframe the result is what
+ * vit_rs_batch_dev / vit_dabplus_aus_dev give for that sub-channel alone on the same bytes: the first-failure rule
+ * (columns at and after the first uncorrectable one stay untouched), the return value, VIT_AU_RS_FAILED gating and
+ * every byte of the record.  Bytes of d_rs_out between the sub-channels' blocks are never written.
+ * vit_rs_table_dev: d_work / d_rs_out in the layout above, d_ret[rec_index[k] + s].
+ * vit_dabplus_aus_table_dev: from_work = 0 reads d_sf in the layout of d_rs_out; from_work = 1 reads it in the layout of
+ * d_work, the first 110 rows of every superframe before RS (with d_ret = NULL: the salvage pass, see
+ * vit_dabplus_aus_dev).  d_au must be 4-byte aligned. */
+int vit_rs_table_dev(const uint8_t *d_work, uint8_t *d_rs_out, int32_t *d_ret,
+                     const vit_ens_subch *h_sub, uint32_t nsub, void *stream);
+int vit_dabplus_aus_table_dev(const uint8_t *d_sf, int from_work, const vit_ens_subch *h_sub, uint32_t nsub,
+                              const int32_t *d_ret /* may be NULL */, vit_au_table *d_au, void *stream);
+/* The chain.  For sub-channel k with layout offsets (wo, ro, ri), take ring_k = ring with first_row advanced by phase
+ * modulo nrows.  DAB+: byte for byte what
+ *   vit_dabplus_ti_superframes_dev(&ring_k, msc_col + col, &profile, erasure, d_work + wo, d_rs_out + ro, d_ret + ri,
+ *                                  d_fire_ok + ri, RSDims, nframes/5, stream);
+ *   vit_dabplus_aus_dev(d_rs_out + ro, 110*RSDims, RSDims, nframes/5, d_ret + ri, d_au + ri, stream);
+ * write; not DAB+: what vit_decode_punctured_ti_dev into d_work + wo followed by vit_energy_dispersal_dev writes.
+ * d_fire_ok and d_au may be NULL (that stage's output is not produced).
+ * Checked on the host before anything is launched (VIT_ERR_ARG): the table as above; the ring as for the *_ti_dev
+ * calls, with rows_needed distinct rows; every sub-channel's columns [msc_col + col, + nsym) inside a row; col a
+ * multiple of 16 (sub-channels start at whole CUs; see "Whole MSC at once" above); profile < nprofiles; the pointers.
+ * d_profiles is a DEVICE array, so the profiles' contents are checked on the device, per frame, as
+ * vit_decode_punctured_varlen_dev does: a frame whose profile is invalid, or whose steps do not sum to framebits + 6,
+ * or which would read beyond its row's span, is skipped - its d_work bytes stay as they were, descrambling included -
+ * and the later stages (fire code, RS, access units) see what d_work held.  vit_punctured_length is the host-side
+ * check of a profile; nsym must be its value (a wrong nsym decodes the wrong columns of the call's own span, never
+ * memory outside it).
+ * Launches: one time de-interleave over the span of columns the table uses, the descriptor table written on the
+ * device from the sub-channel table, the expansion, the decode (device sort and long-frame kernel as
+ * vit_decode_varlen_dev), one descramble + fire code pass, vit_rs_table_dev, vit_dabplus_aus_table_dev.  Scratch (the
+ * calling thread's, as above): (rows_needed - 15) * span bytes, 4*(max_framebits+6) bytes per frame of the table and
+ * two descriptor tables of 24 bytes per frame. */
+int vit_ensemble_dev(const vit_cif_ring *ring, uint64_t msc_col, const vit_ens_subch *h_sub, uint32_t nsub,
+                     const vit_punct_profile *d_profiles, uint32_t nprofiles, uint8_t erasure,
+                     uint8_t *d_work, uint8_t *d_rs_out, int32_t *d_ret, uint8_t *d_fire_ok /* may be NULL */,
+                     vit_au_table *d_au /* may be NULL */, void *stream);
+
 /* From the FFT: differential demodulation, frequency de-interleaving, QPSK demapping and quantisation of whole
  * transmission frames (EN 300 401 clauses 14.5 - 14.7 seen from the receiver) - the step between an FFT on the device and
  * vit_decode_fic_dev / the ring of the *_ti_dev calls.

@@ -30,6 +30,7 @@ EXPORTS = [
     "vit_decode_fic_dev", "vit_dabplus_punctured_superframes_dev",
     "vit_dabplus_aus_dev", "vit_dabplus_aus_host", "vit_fire_code_dev",
     "vit_time_deinterleave_dev", "vit_decode_punctured_ti_dev", "vit_dabplus_ti_superframes_dev",
+    "vit_ensemble_layout", "vit_rs_table_dev", "vit_dabplus_aus_table_dev", "vit_ensemble_dev",
     "vit_freq_interleave_bins", "vit_ofdm_demap_dev",
     "vit_fft_twiddles", "vit_nco_table", "vit_ofdm_fft_dev", "vit_ofdm_demod_dev", "vit_ofdm_sync_dev",
     "vit_ofdm_fft_iq_dev", "vit_ofdm_demod_iq_dev", "vit_ofdm_sync_iq_dev", "vit_iq_convert_dev",
@@ -57,6 +58,14 @@ DESC_DTYPE = np.dtype([("sym_offset", "<u8"), ("out_offset", "<u8"), ("framebits
 AU_DTYPE = np.dtype([("status", "u1"), ("num_aus", "u1"), ("param", "u1"), ("crc_ok", "u1"), ("au_start", "<u2", (7,)),
                      ("fire_ok", "u1"), ("reserved", "u1")])
 AU_OK, AU_RS_FAILED, AU_BAD_HEADER = 0, 1, 2
+
+# vit_ens_subch / vit_ens_layout of include/viterbi_amd.h: one entry per sub-channel of an ensemble, and where its blocks lie
+ENS_MAX_SUBCH = 64
+ENS_SUBCH_DTYPE = np.dtype([("col", "<u4"), ("profile", "<u4"), ("framebits", "<u4"), ("RSDims", "<u4"), ("phase", "<u4"),
+                            ("nframes", "<u4"), ("nsym", "<u4"), ("reserved", "<u4")])
+ENS_LAYOUT_DTYPE = np.dtype([("work_offset", "<u8", (ENS_MAX_SUBCH,)), ("rs_offset", "<u8", (ENS_MAX_SUBCH,)),
+                             ("rec_index", "<u8", (ENS_MAX_SUBCH,)), ("work_bytes", "<u8"), ("rs_bytes", "<u8"), ("nrec", "<u8"),
+                             ("rows_needed", "<u4"), ("max_framebits", "<u4")])
 
 PUNCT_MAX_SEGS = 8
 
@@ -206,6 +215,10 @@ def lib():
         L.vit_time_deinterleave_dev.argtypes = [pr, C.c_uint64, C.c_uint32, vp, C.c_int64, vp]
         L.vit_decode_punctured_ti_dev.argtypes = [pr, C.c_uint64, vp, C.c_uint32, C.c_int64, pp, C.c_uint8, vp]
         L.vit_dabplus_ti_superframes_dev.argtypes = [pr, C.c_uint64, pp, C.c_uint8, vp, vp, vp, vp, C.c_uint32, C.c_int64, vp]
+        L.vit_ensemble_layout.argtypes = [vp, C.c_uint32, vp]
+        L.vit_rs_table_dev.argtypes = [vp, vp, vp, vp, C.c_uint32, vp]
+        L.vit_dabplus_aus_table_dev.argtypes = [vp, C.c_int, vp, C.c_uint32, vp, vp, vp]
+        L.vit_ensemble_dev.argtypes = [pr, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, C.c_uint8, vp, vp, vp, vp, vp, vp]
         L.vit_freq_interleave_bins.argtypes = [C.c_uint32, vp]
         L.vit_freq_interleave_bins.restype = C.c_int64
         L.vit_ofdm_demap_dev.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.POINTER(OfdmShape), C.c_float, C.c_int64, vp, pr,
@@ -573,6 +586,47 @@ def dabplus_ti_superframes_dev(d_ring, first_row, col, profile, d_work, d_rs_out
     _check(lib().vit_dabplus_ti_superframes_dev(C.byref(cif_ring(d_ring, first_row)), col, C.byref(profile), int(erasure),
                                                 _ptr(d_work), _ptr(d_rs_out), _ptr(d_ret), _ptr(d_fire_ok), RSDims, nsf,
                                                 _stream_ptr(stream)), "vit_dabplus_ti_superframes_dev")
+
+
+def _ens_table(sub):
+    """a sub-channel table (ENS_SUBCH_DTYPE array, or anything np.asarray turns into one) -> contiguous array"""
+    return np.ascontiguousarray(np.asarray(sub, ENS_SUBCH_DTYPE).reshape(-1))
+
+
+def ensemble_layout(sub):
+    """host, no GPU: the layout of a sub-channel table (ENS_SUBCH_DTYPE) -> one ENS_LAYOUT_DTYPE record (work_offset,
+    rs_offset, rec_index per entry; work_bytes, rs_bytes, nrec, rows_needed, max_framebits); ViterbiError for a table that
+    breaks a rule of include/viterbi_amd.h"""
+    sub = _ens_table(sub)
+    out = np.zeros(1, ENS_LAYOUT_DTYPE)
+    _check(lib().vit_ensemble_layout(_np(sub), sub.size, _np(out)), "vit_ensemble_layout")
+    return out[0]
+
+
+def rs_table_dev(d_work, d_rs_out, d_ret, sub, stream=None):
+    """batched RScheckSuperframe over every DAB+ sub-channel of the table in one launch: d_work / d_rs_out in the layout
+    of ensemble_layout, d_ret (int32) one value per record"""
+    sub = _ens_table(sub)
+    _check(lib().vit_rs_table_dev(_ptr(d_work), _ptr(d_rs_out), _ptr(d_ret), _np(sub), sub.size, _stream_ptr(stream)),
+           "vit_rs_table_dev")
+
+
+def dabplus_aus_table_dev(d_sf, sub, d_au, d_ret=None, from_work=False, stream=None):
+    """one AU_DTYPE record per superframe of every DAB+ sub-channel of the table in one launch; d_sf in the layout of
+    d_rs_out, or with from_work of d_work (the superframes before RS: the salvage pass, with d_ret None)"""
+    sub = _ens_table(sub)
+    _check(lib().vit_dabplus_aus_table_dev(_ptr(d_sf), 1 if from_work else 0, _np(sub), sub.size, _ptr(d_ret), _ptr(d_au),
+                                           _stream_ptr(stream)), "vit_dabplus_aus_table_dev")
+
+
+def ensemble_dev(d_ring, first_row, msc_col, sub, d_profiles, nprofiles, d_work, d_rs_out, d_ret, d_fire_ok=None, d_au=None,
+                 erasure=128, stream=None):
+    """every sub-channel of the table from the ring in one chain: de-interleave, depuncture (d_profiles: the device
+    image of profiles_bytes), decode, descramble, fire code, RS, access units; outputs in the layout of ensemble_layout"""
+    sub = _ens_table(sub)
+    _check(lib().vit_ensemble_dev(C.byref(cif_ring(d_ring, first_row)), msc_col, _np(sub), sub.size, _ptr(d_profiles),
+                                  nprofiles, int(erasure), _ptr(d_work), _ptr(d_rs_out), _ptr(d_ret), _ptr(d_fire_ok),
+                                  _ptr(d_au), _stream_ptr(stream)), "vit_ensemble_dev")
 
 
 def freq_interleave_bins(nfft):

@@ -134,6 +134,27 @@ __host__ __device__ __forceinline__ u32 fire_remainder(const uint8_t* m9) {
     return r;
 }
 
+// vit_dabplus_post_kernel's loop body for vit_ens_post_kernel (the former keeps its own text, so that its code is what it
+// was): one wavefront descrambles the frame of nb whole bytes at p; if `fire` (wave-uniform) the frame is a superframe's
+// first (nb >= 24: windows 0..3 in the first round) and *flag receives the fire code of its descrambled bytes 0..10,
+// which lanes 0..3 (windows 0..3) hold.
+__device__ __forceinline__ void post_frame(uint8_t* p, u32 nb, u32 lane, const u32* s_prbs, bool fire, uint8_t* flag) {
+    const u32 nw = frame_windows(p, nb);
+    for (u32 s0 = 0; s0 < nw; s0 += WAVE) {
+        const u32 s = s0 + lane;
+        const u32 v = s < nw ? disperse_window(p, nb, 0xFFu, s, s_prbs) : 0u;
+        if (s0 == 0 && fire) {
+            const u32 a = (u32)(reinterpret_cast<uintptr_t>(p) & 3u);
+            const u32 v0 = __shfl(v, 0), v1 = __shfl(v, 1), v2 = __shfl(v, 2), v3 = __shfl(v, 3);
+            const u32 h[3] = {__builtin_amdgcn_alignbyte(v1, v0, a), __builtin_amdgcn_alignbyte(v2, v1, a),
+                              __builtin_amdgcn_alignbyte(v3, v2, a)};
+            uint8_t b[12];
+            __builtin_memcpy(b, h, 12);
+            if (lane == 0) *flag = fire_remainder(b + 2) == ((u32)b[0] << 8 | b[1]) ? 1 : 0;
+        }
+    }
+}
+
 // DAB+ post-pass: 5*nsf frames of 24*rsdims bytes, back to back; every frame dispersed, and the first frame of every
 // superframe also checked by the fire code on its descrambled bytes 0..10, which lanes 0..3 (windows 0..3) hold
 __global__ __launch_bounds__(TPB) void vit_dabplus_post_kernel(uint8_t* __restrict__ work, u32 rsdims, long long nframes,
@@ -291,6 +312,62 @@ __device__ __forceinline__ u32 wave_xor(u32 v) {
 constexpr u32 AU_WPB = TPB / WAVE;
 __host__ __device__ constexpr u32 au_lds_bytes(u32 L) { return ((L + 30u) >> 4) << 4; }  // windows of (15 + L) bytes
 
+// The two halves of vit_au_kernel's loop body, for vit_au_table_kernel (vit_au_kernel keeps its own text, so that its code
+// is what it was before the table form): the superframe of L bytes at p into the wavefront's image s (a = p & 15), and
+// its record from the image (m = s + a: the superframe's byte 0; fbit / fbit2: the lane's fire-code remainders) to the
+// five dwords at rec.
+__device__ __forceinline__ void au_load(const uint8_t* p, u32 L, u32 a, uint8_t* s, u32 lane) {
+    const u32 nwin = (a + L + 15u) >> 4;
+    for (u32 w = lane; w < nwin; w += WAVE) {
+        const int o = (int)(16u * w) - (int)a;
+        if (o >= 0 && (u32)o + 16u <= L) {
+            *reinterpret_cast<uint4*>(s + 16u * w) = *reinterpret_cast<const uint4*>(p + o);
+        } else {
+            for (u32 j = 0; j < 16u; j++) {
+                const int k = o + (int)j;
+                if (k >= 0 && (u32)k < L) s[16u * w + j] = p[k];
+            }
+        }
+    }
+}
+__device__ __forceinline__ void au_eval(const uint8_t* m, u32 L, u32 lane, u32 fbit, u32 fbit2, u32* rec) {
+    // bytes 0..10 into scalars through lanes 0..10
+    const u32 hb = m[lane < 11u ? lane : 0u];
+    u32 b[11];
+#pragma unroll
+    for (u32 k = 0; k < 11u; k++) b[k] = (u32)__builtin_amdgcn_readlane((int)hb, k);
+    const AuHeader h = au_parse(b, L);
+    u32 fv = ((m[2u + (lane >> 3)] >> (7u - (lane & 7u))) & 1u) ? fbit : 0u;
+    fv ^= ((b[10] >> (7u - (lane & 7u))) & 1u) ? fbit2 : 0u;
+    const u32 fire_ok = wave_xor(fv) == (b[0] << 8 | b[1]) ? 1u : 0u;
+    u32 crc_ok = 0;
+    if (h.valid) {
+#pragma unroll
+        for (u32 n = 0; n < 6u; n++) {
+            if (n >= h.num_aus) break;  // wave-uniform
+            const u32 len = h.start[n + 1] - h.start[n] - 2u;  // >= 1 bytes under the CRC
+            const uint8_t* q = m + h.start[n];
+            const u32 c = (len + 63u) >> 6;
+            const int lo = (int)len - (int)((64u - lane) * c), hi = lo + (int)c;
+            u32 r = (lo <= 0 && hi > 0) ? 0xFFFFu : 0u;
+            for (int k = lo > 0 ? lo : 0; k < hi; k++) r = crc16_step(r, q[k]);
+            const u32 x = d_au_pow.v[(63u - lane) * c];
+            u32 prod = 0;
+#pragma unroll
+            for (u32 j = 0; j < 16u; j++) prod ^= ((x >> j) & 1u) ? r << j : 0u;
+            prod = wave_xor(prod);
+            const u32 crc = (prod & 0xFFFFu) ^ crc16_step(crc16_step(prod >> 16, 0), 0);
+            const u32 stored = (u32)q[len] << 8 | q[len + 1u];
+            if ((crc ^ 0xFFFFu) == stored) crc_ok |= 1u << n;
+        }
+    }
+    if (lane < 5u) {
+        u32 w[5];
+        au_record(w, h.valid ? VIT_AU_OK : VIT_AU_BAD_HEADER, h, b[2], crc_ok, fire_ok);
+        rec[lane] = lane == 0u ? w[0] : lane == 1u ? w[1] : lane == 2u ? w[2] : lane == 3u ? w[3] : w[4];
+    }
+}
+
 __global__ __launch_bounds__(TPB) void vit_au_kernel(const uint8_t* __restrict__ sf, u64 stride, u32 rsdims, long long nsf,
                                                      const int32_t* __restrict__ ret, u32* __restrict__ au) {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_au[];
@@ -376,6 +453,75 @@ __global__ __launch_bounds__(TPB) void vit_fire_kernel(const uint8_t* __restrict
     }
 }
 
+// ---- a whole ensemble (vit_internal.h, VitEnsTable): the table forms of the kernels above -----------------------------
+// The descriptor of every frame of the table: frame j of sub-channel k is frame phase + j of the de-interleaved span
+// (`span` bytes per frame), sym0 bytes in, and framebits/8 bytes of the sub-channel's block in d_work.
+__global__ __launch_bounds__(TPB) void vit_ens_desc_kernel(const VitEnsTable tab, const VitEnsSource src, u64 span,
+                                                           vit_frame_desc* __restrict__ desc) {
+    const u32 i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= tab.nframes) return;
+    const u32 k = vit_ens_find<&VitEnsEntry::frame0>(tab, i), j = i - tab.e[k].frame0, fb = tab.e[k].framebits;
+    vit_frame_desc d;
+    d.sym_offset = ((u64)src.phase[k] + j) * span + src.sym0[k];
+    d.out_offset = tab.e[k].work_off + (u64)j * (fb >> 3);
+    d.framebits = fb;
+    d.reserved = src.profile[k];
+    desc[i] = d;
+}
+
+// vit_dabplus_post_kernel over the table: one wavefront per frame, all sub-channels (one that is not DAB+ is descrambled
+// only).  A frame the expansion skipped (idesc[i].framebits 0xFFFFFFFF) keeps its bytes, and its fire code, if it is a
+// superframe's first, is that of the bytes as they are.
+__global__ __launch_bounds__(TPB) void vit_ens_post_kernel(uint8_t* __restrict__ work, const VitEnsTable tab,
+                                                           const vit_frame_desc* __restrict__ idesc,
+                                                           uint8_t* __restrict__ fire_ok) {
+    __shared__ u32 s_prbs[PRBS_WORDS];
+    load_prbs(s_prbs);
+    __syncthreads();
+    const u32 lane = threadIdx.x & (WAVE - 1u);
+    for (u32 i = blockIdx.x * (TPB / WAVE) + (threadIdx.x / WAVE); i < tab.nframes; i += gridDim.x * (TPB / WAVE)) {
+        const u32 k = (u32)__builtin_amdgcn_readfirstlane((int)vit_ens_find<&VitEnsEntry::frame0>(tab, i));
+        const VitEnsEntry& e = tab.e[k];
+        const u32 j = i - e.frame0, nb = e.framebits >> 3;
+        uint8_t* p = work + e.work_off + (u64)j * nb;
+        const bool fire = fire_ok && e.rsdims && j % 5u == 0;
+        if (idesc && idesc[i].framebits == 0xFFFFFFFFu) {
+            if (fire && lane == 0) fire_ok[e.rec0 + j / 5u] = fire_remainder(p + 2) == ((u32)p[0] << 8 | p[1]) ? 1 : 0;
+            continue;
+        }
+        post_frame(p, nb, lane, s_prbs, fire, fire_ok + (e.rec0 + j / 5u));
+    }
+}
+
+// vit_au_kernel over the table: one wavefront per record; its sub-channel gives rsdims and where the superframe lies
+// (from_work: in the work layout, 120*rsdims apart).  The LDS images are sized for the table's largest rsdims.
+__global__ __launch_bounds__(TPB) void vit_au_table_kernel(const uint8_t* __restrict__ sf, u32 from_work, const VitEnsTable tab,
+                                                           const int32_t* __restrict__ ret, u32* __restrict__ au) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t s_au[];
+    const u32 lane = threadIdx.x & (WAVE - 1u), wave = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
+    uint8_t* s = s_au + wave * au_lds_bytes(110u * tab.max_rsdims);
+    const u32 fbit = d_fire_bits.v[lane], fbit2 = lane < 8u ? d_fire_bits.v[64u + lane] : 0u;
+    // every wavefront of a workgroup makes the same number of rounds, as in vit_au_kernel
+    for (u32 f0 = blockIdx.x * AU_WPB; f0 < tab.nrec; f0 += gridDim.x * AU_WPB) {
+        const u32 f = f0 + wave;
+        const bool live = f < tab.nrec;  // wave-uniform
+        const bool read = live && !(ret && ret[live ? f : 0] < 0);
+        const u32 k = (u32)__builtin_amdgcn_readfirstlane((int)vit_ens_find<&VitEnsEntry::rec0>(tab, live ? f : 0u));
+        const VitEnsEntry& e = tab.e[k];
+        const u32 L = 110u * e.rsdims, sfi = (live ? f : 0u) - e.rec0;
+        const uint8_t* p = sf + (from_work ? e.work_off + (u64)sfi * (120u * e.rsdims) : e.rs_off + (u64)sfi * L);
+        const u32 a = (u32)(reinterpret_cast<uintptr_t>(p) & 15u);
+        if (read) au_load(p, L, a, s, lane);
+        __syncthreads();
+        if (read) {
+            au_eval(s + a, L, lane, fbit, fbit2, au + 5u * (u64)f);
+        } else if (live && lane < 5u) {
+            au[5u * (u64)f + lane] = lane == 0u ? (u32)VIT_AU_RS_FAILED : 0u;
+        }
+        __syncthreads();  // the image is read before the next round overwrites it
+    }
+}
+
 unsigned grid_for(long long items, u32 per_block) {
     const long long b = (items + per_block - 1) / per_block;
     return (unsigned)(b < (1 << 20) ? b : (1 << 20));
@@ -450,5 +596,29 @@ hipError_t vit_launch_aus(const uint8_t* d_sf, uint64_t sf_stride, uint32_t rsdi
 hipError_t vit_launch_fire(const uint8_t* d_bytes, uint64_t stride, int64_t n, uint8_t* d_ok, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(vit_fire_kernel, dim3(grid_for(n, TPB)), dim3(TPB), 0, stream, d_bytes, (u64)stride, (long long)n, d_ok);
+    return hipGetLastError();
+}
+
+hipError_t vit_launch_ens_descs(const VitEnsTable& tab, const VitEnsSource& src, uint64_t span, vit_frame_desc* d_desc,
+                                hipStream_t stream) {
+    if (tab.nframes == 0) return hipSuccess;
+    hipLaunchKernelGGL(vit_ens_desc_kernel, dim3((tab.nframes + TPB - 1) / TPB), dim3(TPB), 0, stream, tab, src, (u64)span, d_desc);
+    return hipGetLastError();
+}
+
+hipError_t vit_launch_ens_post(uint8_t* d_work, const VitEnsTable& tab, const vit_frame_desc* d_idesc, uint8_t* d_fire_ok,
+                               hipStream_t stream) {
+    if (tab.nframes == 0) return hipSuccess;
+    hipLaunchKernelGGL(vit_ens_post_kernel, dim3(grid_for(tab.nframes, TPB / WAVE)), dim3(TPB), 0, stream, d_work, tab, d_idesc,
+                       d_fire_ok);
+    return hipGetLastError();
+}
+
+hipError_t vit_launch_aus_table(const uint8_t* d_sf, bool from_work, const VitEnsTable& tab, const int32_t* d_ret,
+                                vit_au_table* d_au, hipStream_t stream) {
+    if (tab.nrec == 0) return hipSuccess;
+    hipLaunchKernelGGL(vit_au_table_kernel, dim3(grid_for(tab.nrec, AU_WPB)), dim3(TPB),
+                       AU_WPB * au_lds_bytes(110u * tab.max_rsdims), stream, d_sf, from_work ? 1u : 0u, tab, d_ret,
+                       reinterpret_cast<u32*>(d_au));
     return hipGetLastError();
 }

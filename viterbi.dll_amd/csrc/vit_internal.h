@@ -159,6 +159,56 @@ hipError_t vit_launch_fire(const uint8_t* d_bytes, uint64_t stride, int64_t n, u
 // semantics after the last output byte, so the host may spin on it instead of synchronising the stream.
 hipError_t rs_launch(const uint8_t* d_p, uint8_t* d_out, int32_t* d_ret, uint32_t rsdims,
                      int64_t nsf, hipStream_t stream, bool host_polls_ret = false);
+// A whole ensemble (include/viterbi_amd.h, vit_ens_subch): the sub-channel table as the kernels read it, BY VALUE in the
+// kernel arguments (2 KB).  Entry k holds where sub-channel k's blocks and its index ranges start; every kernel finds the
+// sub-channel of an index x (a frame, a record, an RS pass) as the largest k whose start is <= x - an entry with an
+// empty range, such as one that is not DAB+ among the records, is never the answer.  The ranges end at the totals.
+struct VitEnsEntry {
+    uint64_t work_off, rs_off;  // vit_ens_layout's
+    uint32_t rec0;              // first record (superframe)
+    uint32_t frame0;            // first frame, all sub-channels counted
+    uint32_t pass0;             // first RS pass: a workgroup pass takes 256 / rsdims superframes of ONE sub-channel
+    uint16_t framebits, rsdims;
+};
+struct VitEnsTable {
+    uint32_t nsub, nframes, nrec, npass;  // the totals
+    uint32_t max_rsdims, pad[3];
+    VitEnsEntry e[VIT_ENS_MAX_SUBCH];
+};
+// vit_ens_find<&VitEnsEntry::frame0>(tab, x): the sub-channel whose frames hold frame x < tab.nframes (rec0, pass0 alike)
+template <uint32_t VitEnsEntry::*START>
+__host__ __device__ inline uint32_t vit_ens_find(const VitEnsTable& tab, uint32_t x) {
+    uint32_t lo = 0, hi = tab.nsub;  // e[0]'s start is 0
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (tab.e[mid].*START <= x) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+// what only the descriptor kernel needs of a sub-channel
+struct VitEnsSource {
+    uint32_t sym0[VIT_ENS_MAX_SUBCH];  // its first column within the de-interleaved span
+    uint32_t phase[VIT_ENS_MAX_SUBCH], profile[VIT_ENS_MAX_SUBCH];
+};
+// The chain's launches, in order (vit_ensemble_dev; the caller has checked every argument rule):
+//   vit_launch_time_deinterleave   the span of columns the table uses, frames 0 ... max(phase + nframes) - 1
+//   vit_launch_ens_descs           d_desc[i] for frame i of the table: its symbols in the de-interleaved copy (frame
+//                                  phase + j of the span, `span` bytes per frame), its bytes in d_work, its profile
+//   vit_launch_depunct_varlen      expansion into the slots, checked descriptors to a second table
+//   launch_decode                  (vit_host.h)
+//   vit_launch_ens_post            every frame descrambled in place, the fire code of every DAB+ superframe's first
+//                                  frame to d_fire_ok (optional); a frame whose checked descriptor (d_idesc, optional) is
+//                                  marked as skipped is not descrambled
+//   rs_table_launch                RS over every DAB+ sub-channel
+//   vit_launch_aus_table           access units; from_work: superframes read from the work layout (120*rsdims apart)
+hipError_t vit_launch_ens_descs(const VitEnsTable& tab, const VitEnsSource& src, uint64_t span, vit_frame_desc* d_desc,
+                                hipStream_t stream);
+hipError_t vit_launch_ens_post(uint8_t* d_work, const VitEnsTable& tab, const vit_frame_desc* d_idesc, uint8_t* d_fire_ok,
+                               hipStream_t stream);
+hipError_t rs_table_launch(const uint8_t* d_work, uint8_t* d_rs_out, int32_t* d_ret, const VitEnsTable& tab, hipStream_t stream);
+hipError_t vit_launch_aus_table(const uint8_t* d_sf, bool from_work, const VitEnsTable& tab, const int32_t* d_ret,
+                                vit_au_table* d_au, hipStream_t stream);
 
 // ---- host-side helpers shared by the TUs -------------------------------------------------------
 // per-thread error text behind vit_last_error() (printf-style)
