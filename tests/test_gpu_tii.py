@@ -27,6 +27,9 @@ NCO_BITS = 12
 # (nfft, Gp, C, R): m mod 3 = 0 with idle threads in the slot stage's workgroup, m mod 3 = 2, 0 and 2 again with 1, 1, 1
 # and 3 slots for some threads
 SHAPES = [(64, 4, 3, 2), (256, 8, 3, 4), (512, 8, 6, 2), (2048, 8, 24, 4)]
+# the other four lengths, so that every instantiation the launcher can choose runs: small geometries and few frames (the
+# model's time); 8192 is the one launch of this call that needs more than 64 KiB of dynamic LDS
+OTHER_SHAPES = [(128, 2, 3, 2), (1024, 4, 5, 2), (4096, 8, 6, 2), (8192, 8, 24, 4)]
 _cache = {}
 
 
@@ -131,6 +134,26 @@ def test_shapes_against_the_model(V, torch_cuda, shape):
             assert (words[:-1, 0] == navg).all() and words[-1, 0] == nframes - (len(words) - 1) * navg
             bits += int(masks_of(words).astype(bool).sum())
     assert bits > 20
+
+
+@pytest.mark.parametrize("shape", OTHER_SHAPES, ids=lambda s: str(s[0]))
+def test_other_lengths_against_the_model(V, torch_cuda, shape):
+    """float32 and CS16 at 3 and 2 frames with navg 2, 1 and 3 (a ragged last group, a group per frame), with and without
+    d_rot and d_energy, windows at odd and even positions through the start table; the masks are not trivial"""
+    nfft, Gp, C_, R = shape
+    x, starts, offset = make_case(shape, nframes=3)
+    pairs = table_of(shape)
+    rot = rot_table(np.random.default_rng(nfft), 3)
+    bits = 0
+    for fmt, combos in ((IQ_F32, [(3, 2), (3, 1)]), (IQ_CS16, [(2, 3), (3, 2)])):
+        samples, mfmt = in_format(x, fmt)
+        for i, (nframes, navg) in enumerate(combos):
+            p = Tii(nfft, Gp, C_, R, navg=navg, thr=2.5, offset=offset)
+            words, _ = run_tii(V, samples, mfmt, p, pairs, nframes, starts=starts, rot=rot if i == 0 else None,
+                               with_energy=(i + fmt) % 2 == 0)
+            assert (words[:-1, 0] == navg).all() and words[-1, 0] == nframes - (len(words) - 1) * navg
+            bits += int(masks_of(words).astype(bool).sum())
+    assert bits > 4
 
 
 @pytest.mark.parametrize("shape", (SHAPES[0], SHAPES[3]), ids=lambda s: str(s[0]))

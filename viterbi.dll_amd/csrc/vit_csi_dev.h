@@ -3,16 +3,18 @@
 // includes it turns contraction off.
 //
 // A symbol's level S is a long sum of the synchroniser's shape: A = max(64, nfft/8) accumulators, one per thread, each
-// the sum of its groups of 4 carriers, meet in the tree of adjacent pairs.  Inside a wavefront the tree is the butterfly
-// over lane distances 1 ... 32: binary32 addition commutes, so lane L's v[L] + v[L ^ h] is the tree's node bit for bit
-// and every lane ends with the wavefront's total.  Distances 1 ... 8 are DPP operands of the addition; 16 and 32 cross
-// DPP rows and go through the LDS crossbar (ds_bpermute).  The wavefronts' totals then meet through CSI_PARTS words of
-// LDS: every thread reads them all (broadcast reads) and finishes the tree itself, so the scale needs no second exchange.
+// the sum of its groups of 4 carriers, meet in the tree of adjacent pairs (vit_wave_dev.h): vit_wave::wave_sum inside a
+// wavefront, then the wavefronts' totals through CSI_PARTS words of LDS, where every thread reads them all (broadcast
+// reads) and finishes the tree itself with vit_wave::pair_tree<TPB / 64>, so the scale needs no second exchange.  A
+// wavefront that holds no accumulator (the demapper's workgroup may be larger than A) leaves the +0 its word starts
+// with: x + 0 = x for the non-negative totals, so the tree over the workgroup's wavefronts is the tree over A/64.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <cfloat>
+
+#include "vit_wave_dev.h"
 
 namespace vit_csi {
 
@@ -26,38 +28,6 @@ __device__ __forceinline__ float csi_term(float nrm) {
 
 // q[g] of the header: the group's four terms in adjacent pairs
 __device__ __forceinline__ float csi_group(float v0, float v1, float v2, float v3) { return (v0 + v1) + (v2 + v3); }
-
-template <int CTRL>
-__device__ __forceinline__ float csi_dpp(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
-
-// the tree of adjacent pairs over the 64 lanes' accumulators; every lane of the wavefront must be active
-__device__ __forceinline__ float csi_wave_sum(float v) {
-    v = v + csi_dpp<0xB1>(v);   // quad_perm [1,0,3,2]: lane ^ 1
-    v = v + csi_dpp<0x4E>(v);   // quad_perm [2,3,0,1]: lane ^ 2
-    v = v + csi_dpp<0x141>(v);  // row_half_mirror: the other quad of the 8, which holds lane ^ 4's value in every lane
-    v = v + csi_dpp<0x140>(v);  // row_mirror: the other half of the row
-    v = v + __shfl_xor(v, 16);
-    v = v + __shfl_xor(v, 32);
-    return v;
-}
-
-// The totals of the workgroup's NW wavefronts from `part` -> S.  A wavefront that holds no accumulator (the demapper's
-// workgroup may be larger than A) leaves the +0 its word starts with: x + 0 = x for the non-negative totals, so the
-// tree over NW is the tree over A/64.
-template <u32 NW>
-__device__ __forceinline__ float csi_block_sum(const float* part) {
-    static_assert(NW >= 1 && NW <= CSI_PARTS && (NW & (NW - 1u)) == 0, "whole wavefronts, a power of two");
-    float u[NW];
-#pragma unroll
-    for (u32 i = 0; i < NW; i++) u[i] = part[i];
-#pragma unroll
-    for (u32 h = 1; h < NW; h *= 2)
-#pragma unroll
-        for (u32 i = 0; i < NW; i += 2u * h) u[i] = u[i] + u[i + h];
-    return u[0];
-}
 
 // s of the header, or 0 for a symbol that is all erasures (S outside [2^-64, 2^96], Inf included; S is never NaN)
 __device__ __forceinline__ float csi_scale(float S, float gain, u32 K) {

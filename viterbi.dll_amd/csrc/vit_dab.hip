@@ -312,10 +312,12 @@ __device__ __forceinline__ u32 wave_xor(u32 v) {
 constexpr u32 AU_WPB = TPB / WAVE;
 __host__ __device__ constexpr u32 au_lds_bytes(u32 L) { return ((L + 30u) >> 4) << 4; }  // windows of (15 + L) bytes
 
-// The two halves of vit_au_kernel's loop body, for vit_au_table_kernel (vit_au_kernel keeps its own text, so that its code
-// is what it was before the table form): the superframe of L bytes at p into the wavefront's image s (a = p & 15), and
-// its record from the image (m = s + a: the superframe's byte 0; fbit / fbit2: the lane's fire-code remainders) to the
-// five dwords at rec.
+// The two halves of vit_au_kernel's loop body, for vit_au_table_kernel: the superframe of L bytes at p into the wavefront's
+// image s (a = p & 15), and its record from the image (m = s + a: the superframe's byte 0; fbit / fbit2: the lane's
+// fire-code remainders) to the five dwords at rec.  vit_au_kernel keeps its own text of them, by measurement
+// (profiles/r19_front_isa_same.txt): once it calls these functions too, the compiler gives au_load the callers' common
+// range of L, and either the table kernel comes out 30 instructions longer and 0.7 % slower in bench_ensemble's table
+// launches (L = 110u * rsdims there), or vit_au_kernel itself 0.7 % slower in bench_au (L from a 16-bit rsdims).
 __device__ __forceinline__ void au_load(const uint8_t* p, u32 L, u32 a, uint8_t* s, u32 lane) {
     const u32 nwin = (a + L + 15u) >> 4;
     for (u32 w = lane; w < nwin; w += WAVE) {

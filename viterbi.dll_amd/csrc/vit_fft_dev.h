@@ -1,6 +1,7 @@
 // vit_fft_dev.h -- the in-LDS FFT of include/viterbi_amd.h ("From the samples", step 2), shared by the kernels that
-// transform a symbol inside a workgroup: vit_ofdm_td.hip (every symbol of a frame) and vit_ofdm_sync.hip (the phase
-// reference symbol and the channel impulse response).  Device code only; a TU that includes it turns contraction off.
+// transform a symbol inside a workgroup: vit_ofdm_td.hip (every symbol of a frame), vit_ofdm_sync.hip (the phase
+// reference symbol and the channel impulse response) and vit_ofdm_tii.hip (the null symbol).  Device code, and the hosts'
+// choice of the instantiation (for_nfft); a TU that includes it turns contraction off.
 //
 // A symbol's FFT lives in LDS as nfft padded float2.  A thread owns 8 points of every pass (nfft/8 threads work on a
 // symbol; at nfft < 512 the rest of the 64 idle in the FFT).  The stages are grouped into passes of 3 (radix-8 in
@@ -10,11 +11,18 @@
 //   other passes 8 LDS loads at stride 2^s, 3 stages, 8 LDS stores in place, a barrier (fft_radix8_passes).
 // The butterflies are the header's radix-2 decimation-in-time graph with the header's twiddles; only the multiplications
 // by the exact twiddles 1 and -j of stages 1 and 2 are skipped (the header's domain makes that free).
-// vit_ofdm_td.hip keeps the two pass loops written out in its kernel, with the rotation fused into the first: its
-// instruction stream stays what it was measured with.  fft_first_pass / fft_radix8_passes are the same loops as functions.
+// vit_ofdm_td.hip keeps both pass loops written out in its kernel, with the rotation fused into the first
+// (profiles/r19_front_isa_same.txt).  As a call, fft_radix8_passes costs six of its 96 instantiations scratch at their
+// 128 VGPRs - mode I's own (nfft 2048, float32, no rotation, per-carrier rule) 0 -> 12 bytes and 114 -> 128 VGPRs, the
+// per-symbol rule's at nfft 1024 ... 4096 12 -> 20, two at nfft 8192 124 -> 132 and 100 -> 108.  fft_first_pass on the
+// rotated samples keeps every instantiation's resources, but together with the soft bytes' destination as a function the
+// per-symbol kernel of the integer formats took 0.2 - 0.3 % longer, and half of the instantiations are the parent's code
+// instruction for instruction with the two written out.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 namespace vit_fft {
 
@@ -111,6 +119,21 @@ constexpr u32 bitrev(u32 x, u32 bits) {
 // LDS index of twiddle k: the lanes of a pass read twiddles a power of two apart
 constexpr u32 twpad(u32 k) { return k + (k >> 5); }
 
+// The workgroup's copy of the table tw (N/2 twiddles) to tw_lds at twpad() - the caller puts a barrier in front of the
+// radix-8 passes - and the two twiddles first_stages needs, e1 and e3, for thread T of Cfg<M>::TPB.  A thread's 7
+// twiddles per pass are the same for every symbol, but 21 or 28 float2 of registers cost more occupancy than their loads
+// cost LDS cycles.
+template <u32 M>
+__device__ __forceinline__ void fft_twiddles_to_lds(float2* tw_lds, const float2* tw, u32 T, float2& e1, float2& e3) {
+    typedef Cfg<M> C;
+    for (u32 i = T; i < C::N / 2u; i += C::TPB) tw_lds[twpad(i)] = tw[i];
+    e1 = e3 = make_float2(1.f, 0.f);
+    if (C::R1 == 3) {
+        e1 = tw[C::N / 8u];
+        e3 = tw[3u * C::N / 8u];
+    }
+}
+
 // the 7 twiddles of thread T's group in the pass behind s stages, in radix8's order, from the LDS copy of the table
 template <u32 M>
 __device__ __forceinline__ void load_twiddles(const float2* tw, u32 T, u32 s, float2 (&w)[7]) {
@@ -168,6 +191,22 @@ __device__ __forceinline__ void fft_radix8_passes(float2* lds, const float2* tw_
         }
         __syncthreads();
     }
+}
+
+// Host side: f(std::integral_constant<u32, M>()) for the transform length nfft = 2^M that has a Cfg<M>
+template <typename F>
+hipError_t for_nfft(u32 nfft, F&& f) {
+    switch (nfft) {
+        case 64: return f(std::integral_constant<u32, 6>());
+        case 128: return f(std::integral_constant<u32, 7>());
+        case 256: return f(std::integral_constant<u32, 8>());
+        case 512: return f(std::integral_constant<u32, 9>());
+        case 1024: return f(std::integral_constant<u32, 10>());
+        case 2048: return f(std::integral_constant<u32, 11>());
+        case 4096: return f(std::integral_constant<u32, 12>());
+        case 8192: return f(std::integral_constant<u32, 13>());
+    }
+    return hipErrorInvalidValue;
 }
 
 }  // namespace vit_fft

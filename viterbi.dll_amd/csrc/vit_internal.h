@@ -218,6 +218,21 @@ int vit_device_cus(int dev);
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device: opt the kernels in once per (device, caller).
 // `done` is the caller's bitmask of devices already handled (guarded by an internal mutex).
 hipError_t vit_optin_dynamic_lds(const void* const* kernels, int nkernels, int bytes, int dev, uint64_t* done);
+// Launches KERNEL with `lds` bytes of dynamic LDS; where that is more than the 64 KiB a kernel gets by default, KERNEL is
+// first opted in on the current device.  KERNEL is a template argument, so every kernel has a `done` mask of its own.
+template <auto KERNEL, typename... Args>
+hipError_t vit_launch_dynamic_lds(unsigned grid, unsigned block, size_t lds, hipStream_t stream, const Args&... args) {
+    if (lds > 64u * 1024u) {
+        static uint64_t optin_done = 0;
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+        const void* ks[1] = {reinterpret_cast<const void*>(KERNEL)};
+        const hipError_t e = vit_optin_dynamic_lds(ks, 1, 160 * 1024, dev, &optin_done);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(block), lds, stream, args...);
+    return hipGetLastError();
+}
 // Restores the calling thread's current HIP device on scope exit (library calls must not leave it changed).
 struct VitDeviceGuard {
     int prev = -1;

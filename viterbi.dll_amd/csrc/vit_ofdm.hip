@@ -16,17 +16,12 @@
 // A table entry >= nfft is ignored and of a repeated entry one n wins: the tile bytes nobody owns keep the erasure
 // value the tiles start with.
 #pragma clang fp contract(off)
-#include <cfloat>
-
-#include "vit_csi_dev.h"
-#include "vit_internal.h"
+#include "vit_demap_dev.h"
 
 namespace {
 
-typedef uint32_t u32;
-typedef uint64_t u64;
+using namespace vit_demap;
 constexpr u32 UNUSED = 0xFFFFu;  // K <= 8192, so no n reaches it
-constexpr u32 RUN_MAX = 25;      // data symbols per workgroup at most: one extra row read per run is then <= 4 %
 
 struct OfdmArgs {
     const float4* fft;         // two carriers per element
@@ -40,21 +35,6 @@ struct OfdmArgs {
     uint8_t* ring;
     u64 row_bytes, nrows, first_row, col;
 };
-
-// the two soft bytes of one carrier (low byte: bit n, next byte: bit n + K) from a = z[l], b = z[l-1]
-__device__ __forceinline__ u32 soft_pair(float ar, float ai, float br, float bi, float gain) {
-    const float re = ar * br + ai * bi;
-    const float im = ai * br - ar * bi;
-    const float nrm = __builtin_fabsf(re) + __builtin_fabsf(im);
-    u32 q = 0x8080u;
-    if (nrm >= 0x1p-64f && nrm <= FLT_MAX) {  // false for NaN
-        const float s = gain / nrm;
-        const float q0 = __builtin_fminf(__builtin_fmaxf(128.0f - __builtin_rintf(re * s), 0.0f), 255.0f);
-        const float q1 = __builtin_fminf(__builtin_fmaxf(128.0f - __builtin_rintf(im * s), 0.0f), 255.0f);
-        q = (u32)q0 | (u32)q1 << 8;
-    }
-    return q;
-}
 
 template <u32 TPB, u32 CPL>
 struct Row {
@@ -101,6 +81,32 @@ __device__ __forceinline__ void demap_symbol(const Row<TPB, CPL>& a, Row<TPB, CP
     }
 }
 
+// The workgroup's start: the erasure value into the tiles, d_bins inverted into `inv`, the first two rows of the run (the
+// one at row0 and the next) into x and y.  Returns `used`.  The lane's chunks are threadIdx.x + j*TPB; their entries (n
+// of the two bins, low half first) stay in LDS.
+template <u32 TPB, u32 CPL>
+__device__ __forceinline__ u32 demap_begin(const OfdmArgs& A, uint8_t* tiles, u32 tb, uint16_t* inv, const float4* row0,
+                                           u32 lane_off, Row<TPB, CPL>& x, Row<TPB, CPL>& y) {
+    for (u32 i = threadIdx.x; i < A.nfft / 2u; i += TPB) reinterpret_cast<u32*>(inv)[i] = UNUSED | UNUSED << 16;
+    for (u32 i = threadIdx.x; i < 2u * tb / 4u; i += TPB) reinterpret_cast<u32*>(tiles)[i] = 0x80808080u;
+    __syncthreads();
+    for (u32 n = threadIdx.x; n < A.K; n += TPB) {
+        const u32 b = A.bins[n];
+        if (b < A.nfft) inv[b] = (uint16_t)n;
+    }
+    __syncthreads();
+    const u32* inv2 = reinterpret_cast<const u32*>(inv);
+    u32 used = 0;
+#pragma unroll
+    for (u32 j = 0; j < CPL; j++) {
+        const u32 c = threadIdx.x + j * TPB;
+        if (2u * c < A.nfft && inv2[c] != 0xFFFFFFFFu) used |= 1u << j;
+    }
+    load_row(row0, lane_off, used, x);
+    load_row(row0 + A.sym_stride2, lane_off, used, y);
+    return used;
+}
+
 // LDS: two tiles of tb bytes (2K rounded up to 16), then nfft u16 of the inverted table.
 template <u32 TPB, u32 CPL>
 __global__ __launch_bounds__(TPB) void vit_ofdm_demap_kernel(OfdmArgs A) {
@@ -111,27 +117,11 @@ __global__ __launch_bounds__(TPB) void vit_ofdm_demap_kernel(OfdmArgs A) {
     const u64 t = blockIdx.x / A.runs;
     const u32 s0 = A.lo + (u32)(blockIdx.x % A.runs) * A.run, s1 = s0 + A.run < A.hi ? s0 + A.run : A.hi;
 
-    for (u32 i = threadIdx.x; i < A.nfft / 2u; i += TPB) reinterpret_cast<u32*>(inv)[i] = UNUSED | UNUSED << 16;
-    for (u32 i = threadIdx.x; i < 2u * tb / 4u; i += TPB) reinterpret_cast<u32*>(tiles)[i] = 0x80808080u;
-    __syncthreads();
-    for (u32 n = threadIdx.x; n < K; n += TPB) {
-        const u32 b = A.bins[n];
-        if (b < A.nfft) inv[b] = (uint16_t)n;
-    }
-    __syncthreads();
-    // the lane's chunks are threadIdx.x + j*TPB; their entries (n of the two bins, low half first) stay in LDS
     const u32* inv2 = reinterpret_cast<const u32*>(inv);
-    u32 used = 0;
-#pragma unroll
-    for (u32 j = 0; j < CPL; j++) {
-        const u32 c = threadIdx.x + j * TPB;
-        if (2u * c < A.nfft && inv2[c] != 0xFFFFFFFFu) used |= 1u << j;
-    }
     const u32 lane_off = threadIdx.x * 16u;
     const float4* frame = A.fft + t * A.frame_stride2;
     Row<TPB, CPL> x, y;  // rows s and s + 1 at even s - s0, rows s + 1 and s at odd
-    load_row(frame + (u64)s0 * A.sym_stride2, lane_off, used, x);
-    load_row(frame + (u64)(s0 + 1u) * A.sym_stride2, lane_off, used, y);
+    const u32 used = demap_begin(A, tiles, tb, inv, frame + (u64)s0 * A.sym_stride2, lane_off, x, y);
     for (u32 s = s0; s < s1; s++) {
         uint8_t* tile = tiles + (s & 1u) * tb;
         const float4* next = s + 1u < s1 ? frame + (u64)(s + 2u) * A.sym_stride2 : nullptr;
@@ -140,16 +130,10 @@ __global__ __launch_bounds__(TPB) void vit_ofdm_demap_kernel(OfdmArgs A) {
         else
             demap_symbol(y, x, next, lane_off, used, inv2, tile, K, A.gain);
         __syncthreads();
-        // the tile's nb bytes to their place: d_fic, or a CIF row of the ring
-        uint8_t* dst;
-        if (s < A.fic_syms) {
-            dst = A.fic + (t * A.fic_syms + s) * nb;
-        } else {
-            const u32 m = s - A.fic_syms, c = m / A.per;
-            u64 row = A.first_row + t * A.cifs + c;
-            if (row >= A.nrows) row -= A.nrows;
-            dst = A.ring + row * A.row_bytes + A.col + (u64)(m - c * A.per) * nb;
-        }
+        // The tile's nb bytes to their place as 16-byte stores of any alignment.  These lines stand in both kernels: as a
+        // function both call, they cost the per-symbol kernels two VGPRs (256 x 4: 84 -> 86) and VIT_SOFT_PER_SYMBOL at
+        // nfft 2048 0.3 % (0.1615 -> 0.1622 ms for 512 frames, profiles/r19_front_isa_same.txt).
+        uint8_t* dst = soft_dst(A, t, s);
         if (nb >= 16u) {
             for (u32 e = threadIdx.x; e < tb / 16u; e += TPB) {
                 const u32 want = 16u * e, a = want < nb - 16u ? want : nb - 16u;  // the last chunk ends at the tile's end
@@ -171,7 +155,7 @@ __global__ __launch_bounds__(TPB) void vit_ofdm_demap_kernel(OfdmArgs A) {
 }
 
 // ---- VIT_SOFT_PER_SYMBOL (include/viterbi_amd.h, "Channel-state weighting") ------------------------------------------
-// A kernel beside the one above, which stays what it was.  A symbol is demapped in two halves around its level S:
+// A kernel beside the one above, with its start.  A symbol is demapped in two halves around its level S:
 //   1. re, im and nrm of the lane's carriers; re and im stay in the lane's registers (0 for an erasure), the term of the
 //      sum goes to position n of a float array in LDS; the chunk of b is dead and receives the next row, as above;
 //   2. the first A = max(64, nfft/8) threads are the header's accumulators: thread i reads groups i and i + A of 4
@@ -233,27 +217,12 @@ __global__ __launch_bounds__(TPB) void vit_ofdm_demap_soft_kernel(OfdmArgs A, So
     const u64 t = blockIdx.x / A.runs;
     const u32 s0 = A.lo + (u32)(blockIdx.x % A.runs) * A.run, s1 = s0 + A.run < A.hi ? s0 + A.run : A.hi;
 
-    for (u32 i = threadIdx.x; i < A.nfft / 2u; i += TPB) reinterpret_cast<u32*>(inv)[i] = UNUSED | UNUSED << 16;
-    for (u32 i = threadIdx.x; i < 2u * tb / 4u; i += TPB) reinterpret_cast<u32*>(tiles)[i] = 0x80808080u;
     for (u32 i = threadIdx.x; i < 4u * ngroups + vit_csi::CSI_PARTS; i += TPB) term[i] = 0.0f;  // an n nobody owns adds +0
-    __syncthreads();
-    for (u32 n = threadIdx.x; n < K; n += TPB) {
-        const u32 b = A.bins[n];
-        if (b < A.nfft) inv[b] = (uint16_t)n;
-    }
-    __syncthreads();
     const u32* inv2 = reinterpret_cast<const u32*>(inv);
-    u32 used = 0;
-#pragma unroll
-    for (u32 j = 0; j < CPL; j++) {
-        const u32 c = threadIdx.x + j * TPB;
-        if (2u * c < A.nfft && inv2[c] != 0xFFFFFFFFu) used |= 1u << j;
-    }
     const u32 lane_off = threadIdx.x * 16u;
     const float4* frame = A.fft + t * A.frame_stride2;
     Row<TPB, CPL> x, y;  // rows s and s + 1 at even s - s0, rows s + 1 and s at odd
-    load_row(frame + (u64)s0 * A.sym_stride2, lane_off, used, x);
-    load_row(frame + (u64)(s0 + 1u) * A.sym_stride2, lane_off, used, y);
+    const u32 used = demap_begin(A, tiles, tb, inv, frame + (u64)s0 * A.sym_stride2, lane_off, x, y);
     for (u32 s = s0; s < s1; s++) {
         uint8_t* tile = tiles + (s & 1u) * tb;
         const float4* next = s + 1u < s1 ? frame + (u64)(s + 2u) * A.sym_stride2 : nullptr;
@@ -274,11 +243,11 @@ __global__ __launch_bounds__(TPB) void vit_ofdm_demap_soft_kernel(OfdmArgs A, So
                 const float4 v = reinterpret_cast<const float4*>(term)[g1];
                 acc = acc + vit_csi::csi_group(v.x, v.y, v.z, v.w);
             }
-            acc = vit_csi::csi_wave_sum(acc);
+            acc = vit_wave::wave_sum(acc);
             if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = acc;
         }
         __syncthreads();
-        const float S = vit_csi::csi_block_sum<TPB / 64u>(part);
+        const float S = vit_wave::pair_tree<TPB / 64u>(part);
         const float sc = vit_csi::csi_scale(S, A.gain, K);
         if (threadIdx.x == 0 && L.level) L.level[t * L.nlev + s] = S;
 #pragma unroll
@@ -297,18 +266,8 @@ __global__ __launch_bounds__(TPB) void vit_ofdm_demap_soft_kernel(OfdmArgs A, So
             }
         }
         __syncthreads();
-        // The tile's nb bytes to their place: d_fic, or a CIF row of the ring.  The kernel above's lines, repeated: moved
-        // into a function that both call, they cost three of its five instantiations a VGPR (27 -> 28, 39 -> 40, 63 -> 64),
-        // and that kernel stays what it was measured with (as vit_ofdm_td.hip keeps its pass loops beside vit_fft_dev.h).
-        uint8_t* dst;
-        if (s < A.fic_syms) {
-            dst = A.fic + (t * A.fic_syms + s) * nb;
-        } else {
-            const u32 m = s - A.fic_syms, c = m / A.per;
-            u64 row = A.first_row + t * A.cifs + c;
-            if (row >= A.nrows) row -= A.nrows;
-            dst = A.ring + row * A.row_bytes + A.col + (u64)(m - c * A.per) * nb;
-        }
+        // the tile's nb bytes to their place: the lines of the kernel above, for the reason given there
+        uint8_t* dst = soft_dst(A, t, s);
         if (nb >= 16u) {
             for (u32 e = threadIdx.x; e < tb / 16u; e += TPB) {
                 const u32 want = 16u * e, a = want < nb - 16u ? want : nb - 16u;  // the last chunk ends at the tile's end
@@ -331,19 +290,9 @@ __global__ __launch_bounds__(TPB) void vit_ofdm_demap_soft_kernel(OfdmArgs A, So
 
 template <u32 TPB, u32 CPL>
 hipError_t launch(const OfdmArgs& A, const SoftArgs* L, u64 grid, size_t lds, hipStream_t stream) {
-    if (L) {
-        if (lds > 64u * 1024u) {  // nfft 8192 with K > 4080: the terms take the kernel past the default limit
-            static uint64_t optin_done = 0;
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-            const void* ks[1] = {reinterpret_cast<const void*>(&vit_ofdm_demap_soft_kernel<TPB, CPL>)};
-            const hipError_t e = vit_optin_dynamic_lds(ks, 1, 160 * 1024, dev, &optin_done);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL((vit_ofdm_demap_soft_kernel<TPB, CPL>), dim3((unsigned)grid), dim3(TPB), lds, stream, A, *L);
-    } else
-        hipLaunchKernelGGL((vit_ofdm_demap_kernel<TPB, CPL>), dim3((unsigned)grid), dim3(TPB), lds, stream, A);
-    return hipGetLastError();
+    // nfft 8192 with K > 4080: the terms take the per-symbol kernel past the default limit of dynamic LDS
+    if (L) return vit_launch_dynamic_lds<&vit_ofdm_demap_soft_kernel<TPB, CPL>>((unsigned)grid, TPB, lds, stream, A, *L);
+    return vit_launch_dynamic_lds<&vit_ofdm_demap_kernel<TPB, CPL>>((unsigned)grid, TPB, lds, stream, A);
 }
 
 }  // namespace
@@ -368,34 +317,9 @@ hipError_t vit_launch_ofdm_demap(const float* d_fft, uint64_t sym_stride, uint64
     A.frame_stride2 = frame_stride / 2u;
     A.bins = d_bins;
     A.nfft = shape.nfft;
-    A.K = shape.ncarriers;
-    A.fic_syms = shape.fic_syms;
-    A.cifs = shape.cifs;
-    A.per = (shape.nsyms - 1u - shape.fic_syms) / shape.cifs;
-    A.lo = d_fic ? 0u : shape.fic_syms;
-    A.hi = ring ? shape.nsyms - 1u : shape.fic_syms;
-    A.gain = gain;
-    A.fic = d_fic;
-    if (ring) {
-        A.ring = const_cast<uint8_t*>(ring->d_base);  // this call is the ring's writer
-        A.row_bytes = ring->row_bytes;
-        A.nrows = ring->nrows;
-        A.first_row = ring->first_row;
-        A.col = col;
-    }
-    if (nframes <= 0 || A.hi <= A.lo) return hipSuccess;
-    // Runs: about 8 workgroups per CU over the whole grid (all the CU can hold: 4 waves each), RUN_MAX symbols at most.
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    const u64 target = 8ull * (u64)vit_device_cus(dev);
-    const u32 nsym = A.hi - A.lo;
-    u64 rpf = (target + (u64)nframes - 1) / (u64)nframes;
-    if (rpf > nsym) rpf = nsym;
-    u32 run = (u32)((nsym + rpf - 1) / rpf);
-    if (run > RUN_MAX) run = RUN_MAX;
-    A.run = run;
-    A.runs = (nsym + run - 1) / run;
-    const u64 grid = (u64)nframes * A.runs;
+    set_outputs(A, shape, gain, d_fic, ring, col);
+    const u64 grid = split_runs(A, nframes);
+    if (grid == 0) return hipSuccess;
     if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
     size_t lds = 2u * (size_t)((2u * A.K + 15u) / 16u * 16u) + 2u * (size_t)A.nfft;
     const SoftArgs soft = {d_level, shape.nsyms - 1u}, *L = rule == VIT_SOFT_PER_SYMBOL ? &soft : nullptr;

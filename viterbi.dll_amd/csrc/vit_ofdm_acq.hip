@@ -21,6 +21,7 @@
 #pragma clang fp contract(off)
 #include "vit_internal.h"
 #include "vit_iq_dev.h"
+#include "vit_wave_dev.h"
 
 namespace {
 
@@ -57,35 +58,13 @@ struct SearchArgs {
     u32* info;
 };
 
-// v + the value of the lane `1 << level` away, level 0 ... 5
-template <u32 CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float xor_add(float v, u32 level) {
-    // after the exchanges below it every lane of a group of 1 << level holds the group's sum, so the mirrors of DPP
-    // fetch what lane ^ 4 and lane ^ 8 hold
-    switch (level) {
-        case 0: return dpp_add<0xB1>(v);   // quad_perm [1, 0, 3, 2]
-        case 1: return dpp_add<0x4E>(v);   // quad_perm [2, 3, 0, 1]
-        case 2: return dpp_add<0x141>(v);  // row_half_mirror
-        case 3: return dpp_add<0x140>(v);  // row_mirror
-        case 4: return v + __shfl_xor(v, 16);
-        default: return v + __shfl_xor(v, 32);
-    }
-}
-
 // the power of the V samples of one chunk: e = fl(fl(re*re) + fl(im*im)), then adjacent pairs
 template <u32 V>
 __device__ __forceinline__ float chunk_power(const float2 (&x)[V]) {
     float e[V];
 #pragma unroll
     for (u32 i = 0; i < V; i++) e[i] = x[i].x * x[i].x + x[i].y * x[i].y;
-#pragma unroll
-    for (u32 h = 1; h < V; h *= 2)
-#pragma unroll
-        for (u32 i = 0; i < V; i += 2u * h) e[i] = e[i] + e[i + h];
-    return e[0];
+    return vit_wave::pair_tree<V>(e);
 }
 
 // the 16 bytes of the chunk at p, which is aligned as a sample of its format is and no more: global loads need no alignment
@@ -138,7 +117,7 @@ __global__ __launch_bounds__(POWER_TPB) void vit_acq_power_kernel(PowerArgs A) {
         for (u32 level = 0; level < 6u; level++)
             if (level < A.lg)
 #pragma unroll
-                for (u32 r = 0; r < ROWS; r++) v[r] = xor_add(v[r], level);
+                for (u32 r = 0; r < ROWS; r++) v[r] = vit_wave::xor_add(v[r], level);
         if (A.lg <= 6u) {
             // lane l of row r holds the sum of its block: chunk c is the first of block c >> lg
             if ((lane & ((1u << A.lg) - 1u)) == 0u)

@@ -23,10 +23,12 @@
 #include "vit_fft_dev.h"
 #include "vit_internal.h"
 #include "vit_iq_dev.h"
+#include "vit_wave_dev.h"
 
 namespace {
 
 using namespace vit_fft;
+using vit_wave::pair_tree;
 
 constexpr u32 MMAX = 64u;              // integer offsets searched at most: -64 ... 64
 constexpr u32 NSHIFT_MAX = 2u * MMAX + 1u;
@@ -64,23 +66,13 @@ struct Scratch {
     static constexpr u32 FLOATS = POWER + 3u * J;
 };
 
-__device__ __forceinline__ float wave_tree_sum(float v) {  // adjacent pairs: every lane ends with the wavefront's total
+// The tree of adjacent pairs over the 64 lanes: every lane ends with the wavefront's total.  vit_wave::wave_sum's bits by six
+// ds_bpermute exchanges instead of four DPP additions and two: with the DPP form the nfft 8192 instantiations, which sit at
+// their 128 VGPRs, spill 28 bytes more (scratch 192 -> 220, profiles/r19_front_isa_same.txt), so this kernel keeps its own.
+__device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (u32 h = 1; h < 64u; h *= 2) v = v + __shfl_xor(v, (int)h);
     return v;
-}
-
-// the tree of adjacent pairs over J values `stride` floats apart
-template <u32 J>
-__device__ __forceinline__ float tree_sum(const float* p, u32 stride) {
-    float u[J];
-#pragma unroll
-    for (u32 i = 0; i < J; i++) u[i] = p[i * stride];
-#pragma unroll
-    for (u32 h = 1; h < J; h *= 2)
-#pragma unroll
-        for (u32 i = 0; i < J; i += 2u * h) u[i] = u[i] + u[i + h];
-    return u[0];
 }
 
 // atan2(im, re) / 2 pi in [-1/2, 1/2]: the header's graph
@@ -169,12 +161,8 @@ __global__ __launch_bounds__(Cfg<M_>::TPB) void vit_ofdm_sync_kernel(SyncArgs A)
         }
         return;
     }
-    for (u32 i = T; i < N / 2u; i += TPB) tw_lds[twpad(i)] = A.tw[i];
-    float2 e1 = make_float2(1.f, 0.f), e3 = e1;
-    if (C::R1 == 3) {
-        e1 = A.tw[N / 8u];
-        e3 = A.tw[3u * N / 8u];
-    }
+    float2 e1, e3;
+    fft_twiddles_to_lds<M_>(tw_lds, A.tw, T, e1, e3);
 
     // ---- A: the guards.  Element e = (l - 1)*Gw + k is the pair at c + l*S - G + W + k = c + nfft + W + (l - 1)*S + k
     const u32 Gw = A.G - 2u * A.W;
@@ -213,18 +201,18 @@ __global__ __launch_bounds__(Cfg<M_>::TPB) void vit_ofdm_sync_kernel(SyncArgs A)
                 en = en + ((a[u].x * a[u].x + a[u].y * a[u].y) + (b[u].x * b[u].x + b[u].y * b[u].y));
             }
     }
-    gr = wave_tree_sum(gr);
-    gi = wave_tree_sum(gi);
-    en = wave_tree_sum(en);
+    gr = wave_sum(gr);
+    gi = wave_sum(gi);
+    en = wave_sum(en);
     if (lane == 0) {
         scr[S::GUARDS + wave] = gr;
         scr[S::GUARDS + J + wave] = gi;
         scr[S::GUARDS + 2u * J + wave] = en;
     }
     __syncthreads();  // and the twiddles are in LDS
-    gr = tree_sum<J>(scr + S::GUARDS, 1u);
-    gi = tree_sum<J>(scr + S::GUARDS + J, 1u);
-    en = tree_sum<J>(scr + S::GUARDS + 2u * J, 1u);
+    gr = pair_tree<J>(scr + S::GUARDS);
+    gi = pair_tree<J>(scr + S::GUARDS + J);
+    en = pair_tree<J>(scr + S::GUARDS + 2u * J);
     const float turn = turn_of(gr, gi);
     const float scale = (float)(1u << (32u - M_));  // 2^32 / nfft
     const u32 step_frac = 0u - (u32)(int)__builtin_rintf(turn * scale);
@@ -281,7 +269,7 @@ __global__ __launch_bounds__(Cfg<M_>::TPB) void vit_ofdm_sync_kernel(SyncArgs A)
         }
 #pragma unroll
         for (u32 a = 0; a < SHIFT_GROUP; a++) {
-            const float re = wave_tree_sum(acc[a].x), im = wave_tree_sum(acc[a].y);
+            const float re = wave_sum(acc[a].x), im = wave_sum(acc[a].y);
             if (lane == 0 && g0 + a < nshift) {
                 scr[S::SHIFTS + ((g0 + a) * J + wave) * 2u] = re;
                 scr[S::SHIFTS + ((g0 + a) * J + wave) * 2u + 1u] = im;
@@ -290,8 +278,8 @@ __global__ __launch_bounds__(Cfg<M_>::TPB) void vit_ofdm_sync_kernel(SyncArgs A)
     }
     __syncthreads();
     for (u32 i = T; i < nshift; i += TPB) {
-        const float re = tree_sum<J>(scr + S::SHIFTS + i * J * 2u, 2u);
-        const float im = tree_sum<J>(scr + S::SHIFTS + i * J * 2u + 1u, 2u);
+        const float re = pair_tree<J>(scr + S::SHIFTS + i * J * 2u, 2u);
+        const float im = pair_tree<J>(scr + S::SHIFTS + i * J * 2u + 1u, 2u);
         scr[S::METRIC + i] = re * re + im * im;
     }
     __syncthreads();
@@ -331,7 +319,7 @@ __global__ __launch_bounds__(Cfg<M_>::TPB) void vit_ofdm_sync_kernel(SyncArgs A)
         psum = psum + pw[j];
         if (n <= 2u * A.W && pw[j] > pmax) pmax = pw[j];
     }
-    psum = wave_tree_sum(psum);
+    psum = wave_sum(psum);
 #pragma unroll
     for (u32 h = 1; h < 64u; h *= 2) {
         const float o = __shfl_xor(pmax, (int)h);
@@ -342,7 +330,7 @@ __global__ __launch_bounds__(Cfg<M_>::TPB) void vit_ofdm_sync_kernel(SyncArgs A)
         scr[S::POWER + J + wave] = pmax;
     }
     __syncthreads();
-    psum = tree_sum<J>(scr + S::POWER, 1u);
+    psum = pair_tree<J>(scr + S::POWER);
 #pragma unroll
     for (u32 i = 0; i < J; i++) {
         const float o = scr[S::POWER + J + i];
@@ -387,16 +375,7 @@ template <u32 M_, bool INT>
 hipError_t launch_sync2(const SyncArgs& A, int64_t nframes, hipStream_t stream) {
     typedef Cfg<M_> C;
     const size_t lds = C::LDS_BYTES + Scratch<C::TPB / 64u>::FLOATS * 4u;
-    if (lds > 64u * 1024u) {
-        static uint64_t optin_done = 0;
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        const void* ks[1] = {reinterpret_cast<const void*>(&vit_ofdm_sync_kernel<M_, INT>)};
-        const hipError_t e = vit_optin_dynamic_lds(ks, 1, 160 * 1024, dev, &optin_done);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((vit_ofdm_sync_kernel<M_, INT>), dim3((unsigned)nframes), dim3(C::TPB), lds, stream, A);
-    return hipGetLastError();
+    return vit_launch_dynamic_lds<&vit_ofdm_sync_kernel<M_, INT>>((unsigned)nframes, C::TPB, lds, stream, A);
 }
 
 template <u32 M_>
@@ -433,15 +412,5 @@ hipError_t vit_launch_ofdm_sync(const vit_iq_input& in, const vit_iq_format& fmt
     A.info = d_info;
     A.iq_fmt = fmt.format;
     A.iq_scale = fmt.scale;
-    switch (p.nfft) {
-        case 64: return launch_sync<6>(A, nframes, stream);
-        case 128: return launch_sync<7>(A, nframes, stream);
-        case 256: return launch_sync<8>(A, nframes, stream);
-        case 512: return launch_sync<9>(A, nframes, stream);
-        case 1024: return launch_sync<10>(A, nframes, stream);
-        case 2048: return launch_sync<11>(A, nframes, stream);
-        case 4096: return launch_sync<12>(A, nframes, stream);
-        case 8192: return launch_sync<13>(A, nframes, stream);
-    }
-    return hipErrorInvalidValue;
+    return for_nfft(p.nfft, [&](auto m) { return launch_sync<decltype(m)::value>(A, nframes, stream); });
 }

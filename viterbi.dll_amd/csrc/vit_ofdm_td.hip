@@ -12,6 +12,8 @@
 //   first pass   straight from the sample registers: thread T holds samples T + c*nfft/R, which bit reversal makes the
 //                R consecutive points of group bitrev(T); rotation, stages 1 ... log2 R, one LDS store per point;
 //   other passes 8 LDS loads at stride 2^s, 3 stages, 8 LDS stores in place, a barrier.
+// Both pass loops are written out here, with the rotation fused into the first: vit_fft_dev.h has them as functions
+// and the measured reason.
 // The twiddle table is copied to LDS behind the symbol once per workgroup and a thread loads its 7 twiddles per radix-8
 // pass from there: they are the same for every symbol, but kept in registers (21 float2 at nfft 2048) they cost a
 // wavefront per SIMD, which costs more than the loads.  The next symbol's samples (and phasors) are loaded right after
@@ -19,26 +21,24 @@
 // Demapping: carrier n reads bin d_bins[n] of the LDS spectrum; a thread owns fixed groups of 4 consecutive n, keeps
 // their bins and the previous symbol's values in registers and stores 4 + 4 soft bytes per group (any alignment).  A run
 // starts by transforming the symbol before it: 1/run of redundant work.
-// Integer sample formats (vit_iq_dev.h): one template flag apart from the float32 instantiations, which stay what they
-// were.  The prefetched samples are then kept raw, 8 dwords instead of 16, and converted where the first pass consumes
+// Integer sample formats (vit_iq_dev.h): one template flag apart from the float32 instantiations, which pay nothing for
+// them.  The prefetched samples are then kept raw, 8 dwords instead of 16, and converted where the first pass consumes
 // them; the three formats share an instantiation and part in two scalar branches of the loader.
-// The per-symbol soft-decision rule (VIT_SOFT_PER_SYMBOL, vit_csi_dev.h): one more template flag, the other instantiations
-// stay what they were.  The thread's groups T + j*TPB are the header's groups of accumulator T (TPB = max(64, nfft/8)), so
+// The per-symbol soft-decision rule (VIT_SOFT_PER_SYMBOL, vit_csi_dev.h): one more template flag, of which the other
+// instantiations hold no code.  The thread's groups T + j*TPB are the header's groups of accumulator T (TPB = max(64, nfft/8)), so
 // it keeps re and im of its 8 carriers, sums their terms, the workgroup reduces (DPP inside a wavefront, one LDS exchange
 // and one barrier across them, CSI_PARTS floats behind the twiddles) and every thread quantises with the symbol's scale.
 #pragma clang fp contract(off)
-#include <cfloat>
 #include <cmath>
 
-#include "vit_csi_dev.h"
+#include "vit_demap_dev.h"
 #include "vit_fft_dev.h"
-#include "vit_internal.h"
 #include "vit_iq_dev.h"
 
 namespace {
 
 using namespace vit_fft;
-constexpr u32 RUN_MAX = 25;  // data symbols per workgroup at most: one extra transform per run is then <= 4 %
+using namespace vit_demap;
 
 struct TdArgs {
     const float2* iq;
@@ -67,22 +67,6 @@ struct TdArgs {
     float* level;
     u32 nlev, csi;  // csi: host side only, picks the instantiation
 };
-
-
-// the two soft bytes of one carrier (low byte: bit n, next byte: bit n + K) from a = z[l], b = z[l-1]: vit_ofdm.hip's
-__device__ __forceinline__ u32 soft_pair(float ar, float ai, float br, float bi, float gain) {
-    const float re = ar * br + ai * bi;
-    const float im = ai * br - ar * bi;
-    const float nrm = __builtin_fabsf(re) + __builtin_fabsf(im);
-    u32 q = 0x8080u;
-    if (nrm >= 0x1p-64f && nrm <= FLT_MAX) {  // false for NaN
-        const float s = gain / nrm;
-        const float q0 = __builtin_fminf(__builtin_fmaxf(128.0f - __builtin_rintf(re * s), 0.0f), 255.0f);
-        const float q1 = __builtin_fminf(__builtin_fmaxf(128.0f - __builtin_rintf(im * s), 0.0f), 255.0f);
-        q = (u32)q0 | (u32)q1 << 8;
-    }
-    return q;
-}
 
 template <u32 M, bool ROT, bool INT>
 struct Samples {
@@ -142,18 +126,12 @@ __global__ __launch_bounds__(Cfg<M>::TPB) __attribute__((amdgpu_waves_per_eu(Cfg
         step = r.y;
     }
 
-    // the twiddles live in LDS behind the symbol (a thread's 7 per pass are the same for every symbol, but 21 or 28
-    // float2 of registers cost more occupancy than their loads cost LDS cycles)
     static_assert(pad_is_affine(M), "pad() must skew every thread's group alike");
-    float2* tw_lds = lds_td + Cfg<M>::PADN;
-    for (u32 i = T; i < N / 2u; i += C::TPB) tw_lds[twpad(i)] = A.tw[i];
+    float2* tw_lds = lds_td + Cfg<M>::PADN;  // the twiddles live in LDS behind the symbol
+    float2 e1, e3;
+    fft_twiddles_to_lds<M>(tw_lds, A.tw, T, e1, e3);
     float* part = reinterpret_cast<float*>(lds_td) + C::LDS_BYTES / 4u;  // CSI: the wavefronts' totals, +0 behind the last
     if (CSI && T < vit_csi::CSI_PARTS) part[T] = 0.0f;
-    float2 e1 = make_float2(1.f, 0.f), e3 = e1;
-    if (R1 == 3) {
-        e1 = A.tw[N / 8u];
-        e3 = A.tw[3u * N / 8u];
-    }
     __syncthreads();
     // the thread's carriers: groups T + j*TPB of 4 consecutive n
     u32 bin[C::CG][4];
@@ -196,7 +174,7 @@ __global__ __launch_bounds__(Cfg<M>::TPB) __attribute__((amdgpu_waves_per_eu(Cfg
         }
         __syncthreads();
 #pragma unroll
-        for (u32 p = 0; p < NP; p++) {
+        for (u32 p = 0; p < NP; p++) {  // fft_radix8_passes' loop, written out: vit_fft_dev.h has the measured reason
             if (active) {
                 const u32 s = R1 + 3u * p;
                 float2* g = lds_td + pad(pass_base(T, s));
@@ -213,6 +191,8 @@ __global__ __launch_bounds__(Cfg<M>::TPB) __attribute__((amdgpu_waves_per_eu(Cfg
         }
         if (DEMAP) {
             const u32 s = l - 1u;  // the data symbol this transform completes (none at l = s0)
+            // soft_dst(A, t, s) written out: through the function the integer formats' per-symbol kernel at nfft 2048 took
+            // 0.2 - 0.3 % longer (0.2122 -> 0.2127 ms for 512 frames, profiles/r19_front_isa_same.txt)
             uint8_t* dst = nullptr;
             if (l > s0) {
                 if (s < A.fic_syms) {
@@ -247,10 +227,10 @@ __global__ __launch_bounds__(Cfg<M>::TPB) __attribute__((amdgpu_waves_per_eu(Cfg
                     acc = j ? acc + q : q;  // a group at or beyond K adds +0
                 }
                 if (dst) {  // uniform: every symbol of the run but the one before it
-                    acc = vit_csi::csi_wave_sum(acc);
+                    acc = vit_wave::wave_sum(acc);
                     if ((T & 63u) == 0) part[T >> 6] = acc;
                     __syncthreads();
-                    const float S = vit_csi::csi_block_sum<C::TPB / 64u>(part);
+                    const float S = vit_wave::pair_tree<C::TPB / 64u>(part);
                     sc = vit_csi::csi_scale(S, A.gain, A.K);
                     if (T == 0 && A.level) A.level[t * A.nlev + s] = S;
                 }
@@ -300,16 +280,7 @@ __global__ __launch_bounds__(Cfg<M>::TPB) __attribute__((amdgpu_waves_per_eu(Cfg
 template <u32 M, bool ROT, bool DEMAP, bool INT, bool CSI = false>
 hipError_t launch3(const TdArgs& A, u64 grid, hipStream_t stream) {
     const size_t lds = Cfg<M>::LDS_BYTES + (CSI ? 4u * vit_csi::CSI_PARTS : 0u);
-    if (lds > 64u * 1024u) {
-        static uint64_t optin_done = 0;
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        const void* ks[1] = {reinterpret_cast<const void*>(&vit_ofdm_td_kernel<M, ROT, DEMAP, INT, CSI>)};
-        const hipError_t e = vit_optin_dynamic_lds(ks, 1, 160 * 1024, dev, &optin_done);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((vit_ofdm_td_kernel<M, ROT, DEMAP, INT, CSI>), dim3((unsigned)grid), dim3(Cfg<M>::TPB), lds, stream, A);
-    return hipGetLastError();
+    return vit_launch_dynamic_lds<&vit_ofdm_td_kernel<M, ROT, DEMAP, INT, CSI>>((unsigned)grid, Cfg<M>::TPB, lds, stream, A);
 }
 
 template <u32 M, bool INT>
@@ -324,32 +295,12 @@ hipError_t launch2(const TdArgs& A, bool demap, u64 grid, hipStream_t stream) {
     return A.iq_fmt == VIT_IQ_F32 ? launch2i<M, false>(A, demap, grid, stream) : launch2i<M, true>(A, demap, grid, stream);
 }
 
-// workgroups of the TdArgs' symbol range: about 8 per CU over the whole grid, RUN_MAX symbols per run at most
+// the symbols [lo, hi) of every frame, split into runs (vit_demap_dev.h), by the instantiation for nfft
 hipError_t launch(TdArgs& A, u32 nfft, bool demap, int64_t nframes, hipStream_t stream) {
-    if (nframes <= 0 || A.hi <= A.lo) return hipSuccess;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    const u64 target = 8ull * (u64)vit_device_cus(dev);
-    const u32 nsym = A.hi - A.lo;
-    u64 rpf = (target + (u64)nframes - 1) / (u64)nframes;
-    if (rpf > nsym) rpf = nsym;
-    u32 run = (u32)((nsym + rpf - 1) / rpf);
-    if (run > RUN_MAX) run = RUN_MAX;
-    A.run = run;
-    A.runs = (nsym + run - 1) / run;
-    const u64 grid = (u64)nframes * A.runs;
+    const u64 grid = split_runs(A, nframes);
+    if (grid == 0) return hipSuccess;
     if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    switch (nfft) {
-        case 64: return launch2<6>(A, demap, grid, stream);
-        case 128: return launch2<7>(A, demap, grid, stream);
-        case 256: return launch2<8>(A, demap, grid, stream);
-        case 512: return launch2<9>(A, demap, grid, stream);
-        case 1024: return launch2<10>(A, demap, grid, stream);
-        case 2048: return launch2<11>(A, demap, grid, stream);
-        case 4096: return launch2<12>(A, demap, grid, stream);
-        case 8192: return launch2<13>(A, demap, grid, stream);
-    }
-    return hipErrorInvalidValue;
+    return for_nfft(nfft, [&](auto m) { return launch2<decltype(m)::value>(A, demap, grid, stream); });
 }
 
 TdArgs input_args(const vit_iq_input& in, const vit_iq_format& fmt, u32 nfft, u32 nsyms) {
@@ -418,23 +369,9 @@ hipError_t vit_launch_ofdm_demod(const vit_iq_input& in, const vit_iq_format& fm
                                  hipStream_t stream) {
     TdArgs A = input_args(in, fmt, shape.nfft, shape.nsyms);
     A.bins = d_bins;
-    A.K = shape.ncarriers;
-    A.fic_syms = shape.fic_syms;
-    A.cifs = shape.cifs;
-    A.per = (shape.nsyms - 1u - shape.fic_syms) / shape.cifs;
-    A.lo = d_fic ? 0u : shape.fic_syms;
-    A.hi = ring ? shape.nsyms - 1u : shape.fic_syms;
-    A.gain = gain;
-    A.fic = d_fic;
+    set_outputs(A, shape, gain, d_fic, ring, col);
     A.csi = rule == VIT_SOFT_PER_SYMBOL;
     A.level = d_level;
     A.nlev = shape.nsyms - 1u;
-    if (ring) {
-        A.ring = const_cast<uint8_t*>(ring->d_base);  // this call is the ring's writer
-        A.row_bytes = ring->row_bytes;
-        A.nrows = ring->nrows;
-        A.first_row = ring->first_row;
-        A.col = col;
-    }
     return launch(A, shape.nfft, true, nframes, stream);
 }

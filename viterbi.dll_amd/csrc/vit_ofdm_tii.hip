@@ -74,12 +74,8 @@ __global__ __launch_bounds__(Cfg<M_>::TPB) void vit_tii_spectrum_kernel(TiiArgs 
     const u64 t = blockIdx.x;
     u64 w0 = 0;
     if (!window_of(A, t, w0)) return;  // uniform over the workgroup
-    for (u32 i = T; i < N / 2u; i += TPB) tw_lds[twpad(i)] = A.tw[i];
-    float2 e1 = make_float2(1.f, 0.f), e3 = e1;
-    if (C::R1 == 3) {
-        e1 = A.tw[N / 8u];
-        e3 = A.tw[3u * N / 8u];
-    }
+    float2 e1, e3;
+    fft_twiddles_to_lds<M_>(tw_lds, A.tw, T, e1, e3);
     if (active) {
         float2 x[8];
         if constexpr (INT) {
@@ -182,17 +178,7 @@ __global__ __launch_bounds__(GROUP_TPB) void vit_tii_group_kernel(TiiArgs A) {
 template <u32 M_, bool INT>
 hipError_t launch_tii2(const TiiArgs& A, hipStream_t stream) {
     typedef Cfg<M_> C;
-    const size_t lds = C::LDS_BYTES;
-    if (lds > 64u * 1024u) {
-        static uint64_t optin_done = 0;
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        const void* ks[1] = {reinterpret_cast<const void*>(&vit_tii_spectrum_kernel<M_, INT>)};
-        const hipError_t e = vit_optin_dynamic_lds(ks, 1, 160 * 1024, dev, &optin_done);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((vit_tii_spectrum_kernel<M_, INT>), dim3((unsigned)A.nframes), dim3(C::TPB), lds, stream, A);
-    hipError_t e = hipGetLastError();
+    hipError_t e = vit_launch_dynamic_lds<&vit_tii_spectrum_kernel<M_, INT>>((unsigned)A.nframes, C::TPB, C::LDS_BYTES, stream, A);
     if (e != hipSuccess) return e;
     const long long ngrp = (A.nframes + A.navg - 1) / A.navg;
     hipLaunchKernelGGL(vit_tii_group_kernel, dim3((unsigned)ngrp), dim3(GROUP_TPB), 0, stream, A);
@@ -234,15 +220,5 @@ hipError_t vit_launch_ofdm_tii(const vit_iq_input& in, const vit_iq_format& fmt,
     A.energy = d_energy;
     A.iq_fmt = fmt.format;
     A.iq_scale = fmt.scale;
-    switch (p.nfft) {
-        case 64: return launch_tii<6>(A, stream);
-        case 128: return launch_tii<7>(A, stream);
-        case 256: return launch_tii<8>(A, stream);
-        case 512: return launch_tii<9>(A, stream);
-        case 1024: return launch_tii<10>(A, stream);
-        case 2048: return launch_tii<11>(A, stream);
-        case 4096: return launch_tii<12>(A, stream);
-        case 8192: return launch_tii<13>(A, stream);
-    }
-    return hipErrorInvalidValue;
+    return for_nfft(p.nfft, [&](auto m) { return launch_tii<decltype(m)::value>(A, stream); });
 }

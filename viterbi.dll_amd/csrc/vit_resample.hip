@@ -240,16 +240,7 @@ hipError_t launch(bool direct, unsigned grid, size_t lds, hipStream_t stream, co
         hipLaunchKernelGGL((vit_resample_kernel<FMT, true>), dim3(grid), dim3(TPB), 0, stream, A);
         return hipGetLastError();
     }
-    if (lds > 64u * 1024u) {
-        static uint64_t optin_done = 0;
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        const void* ks[1] = {reinterpret_cast<const void*>(&vit_resample_kernel<FMT, false>)};
-        const hipError_t e = vit_optin_dynamic_lds(ks, 1, 160 * 1024, dev, &optin_done);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((vit_resample_kernel<FMT, false>), dim3(grid), dim3(TPB), lds, stream, A);
-    return hipGetLastError();
+    return vit_launch_dynamic_lds<&vit_resample_kernel<FMT, false>>(grid, TPB, lds, stream, A);
 }
 
 }  // namespace
