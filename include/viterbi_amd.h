@@ -438,6 +438,81 @@ int vit_ensemble_dev(const vit_cif_ring *ring, uint64_t msc_col, const vit_ens_s
                      uint8_t *d_work, uint8_t *d_rs_out, int32_t *d_ret, uint8_t *d_fire_ok /* may be NULL */,
                      vit_au_table *d_au /* may be NULL */, void *stream);
 
+/* Packet mode (EN 300 401 clause 5.3): data sub-channels - the third kind beside DAB+ and DAB audio - and the forward
+ * error correction of enhanced packet mode.  The definitions below are the library's, written without the standard's
+ * text at hand; they are what these calls promise and what the tests check.  Each constant stands once in
+ * csrc/vit_packet_fmt.h.
+ * The stream: a packet-mode sub-channel's descrambled logical frames back to back, framebytes each, a multiple of 24 in
+ * 24 ... 1152 - the d_work block of an RSDims 0 entry of vit_ensemble_dev from work_offset[k] on, or the output of the
+ * decode calls after vit_energy_dispersal_dev.  It is a run of 24-byte slots, slot i = bytes 24i ... 24i+23.
+ * Common rules: errors as above (VIT_ERR_NO_DEVICE first, VIT_ERR_ARG with vit_last_error()); everything is enqueued on
+ * `stream` without synchronising; an empty batch (nslots or nframes 0) returns VIT_OK and writes nothing; byte pointers
+ * may have any alignment, record and score pointers must be 4-byte aligned; no byte outside the named ranges is read or
+ * written.
+ *
+ * A packet: 1 ... 4 slots.
+ *   byte 0   bits 7..6 length (0 ... 3: 24, 48, 72, 96 bytes), bits 5..4 continuity index, bits 3..2 first/last,
+ *            bits 1..0 address bits 9..8
+ *   byte 1   address bits 7..0; address 0 is padding, address 1022 an FEC packet (always one slot)
+ *   byte 2   bit 7 command, bits 6..0 useful data length
+ *   last two bytes: the ones' complement of the CRC-16 of the FIB check (0x1021, preset 0xFFFF, MSB first) over all the
+ *            bytes before them
+ * An FEC frame: 103 slots = 94 slots of application data (2256 bytes), then 9 FEC packets.  FEC packet c (0 ... 8) has
+ * byte 0 = c<<2 | 3 and byte 1 = 0xFE (length 0, a 4-bit counter in bits 5..2, address 1022), then 22 parity bytes.
+ *   table    12 rows of 188 data columns, filled column by column: row r, column c = frame byte 12c + r
+ *   parity   16 bytes per row; parity byte j of row r is RS-data byte m = 12j + r, at byte 2 + m % 22 of FEC packet
+ *            m / 22; the last 6 bytes of FEC packet 8 are padding.  Padding and the nine headers are never changed.
+ *   code     each row of 204 bytes is a codeword of RS(204,188) over GF(2^8), field polynomial 0x11D, alpha = 2,
+ *            g(x) = prod_{i=0..15} (x + alpha^i), shortened from (255,239) by 51 leading zero bytes; column 0 is the
+ *            highest-degree coefficient, parity byte 15 the constant term
+ *   result   if a codeword of the shortened code lies within Hamming distance 8 of the row's 204 bytes (it is then the
+ *            only one), every byte that differs is replaced by the codeword's, parity included, and nerr[r] is the
+ *            distance (0 ... 8); otherwise the row stays as it was and nerr[r] = -1.  A nearest full-length codeword that
+ *            differs in the 51 padding positions is such a failure, not a correction. */
+typedef struct vit_fec_rec {   /* 16 bytes per FEC frame, written completely */
+    int8_t   nerr[12];
+    uint16_t hdr_ok;           /* bit c: FEC packet c's two header bytes are as expected (decoding does not depend on it) */
+    uint8_t  status;           /* 0: all rows decoded; 1: at least one row failed */
+    uint8_t  reserved;         /* 0 */
+} vit_fec_rec;
+#define VIT_PKT_CONT    0   /* slot inside a longer packet; every other field 0 */
+#define VIT_PKT_DATA    1   /* a packet starts here; address not 0 and not 1022 */
+#define VIT_PKT_PADDING 2   /* address 0; CRC still checked, the other fields as for a data packet */
+#define VIT_PKT_FEC     3   /* address 1022: one slot whatever its length bits say, no CRC (crc_ok 0), nslots 1,
+                               flags = the 4-bit counter (byte 0 bits 5..2), useful 0 */
+#define VIT_PKT_OVERRUN 4   /* the length claimed here runs past the frame's end: this slot and every later slot of the
+                               frame, other fields 0 */
+typedef struct vit_packet_rec {   /* 8 bytes per slot, written completely */
+    uint8_t  kind, crc_ok, nslots /* 1..4 at a start */, flags /* bits 1..0 continuity, 3..2 first/last, 4 command */;
+    uint16_t address;
+    uint8_t  useful, reserved;
+} vit_packet_rec;
+/* Where the FEC frames lie: d_score[p], p = 0 ... 102, = the number of slots i < nslots with (i - p) mod 103 >= 94 whose
+ * first two bytes are the header of FEC packet (i - p) mod 103 - 94.  The caller takes the phase from the largest score
+ * (the analogue of vit_fire_code_dev).  All 103 words are written (cleared on the stream, then added to).  d_stream is
+ * only read, two bytes of each slot. */
+int vit_packet_fec_sync_dev(const uint8_t *d_stream, int64_t nslots, uint32_t *d_score /* uint32[103] */, void *stream);
+/* Whole FEC frames in nslots slots from `phase` on: (nslots - phase) / 103, 0 if nslots <= phase; -1 for nslots < 0 or
+ * phase > 102.  Host only. */
+int64_t vit_packet_fec_count(int64_t nslots, uint32_t phase);
+/* phase 0 ... 102: FEC frame k occupies slots phase + 103k ... phase + 103k + 102; the nfec = vit_packet_fec_count(nslots,
+ * phase) whole frames are decoded (a partial frame at the end is not), one record each.  d_out is d_stream itself (in
+ * place) or does not overlap it; out of place every one of the 24*nslots bytes that is not rewritten is copied, also
+ * when nfec is 0.  d_fec may be NULL when nfec is 0.  A lane per (frame, row), 20 frames per workgroup; in place, a
+ * workgroup whose rows are all clean writes no byte of the stream.  Across calls the phase is the caller's:
+ * (phase - slots consumed) mod 103. */
+int vit_packet_fec_dev(const uint8_t *d_stream, uint8_t *d_out, int64_t nslots, uint32_t phase,
+                       vit_fec_rec *d_fec /* vit_fec_rec[nfec] */, void *stream);
+/* Host only, needs no GPU: the same definition for one FEC frame of 2472 bytes, in place.  VIT_ERR_ARG for a NULL
+ * pointer. */
+int vit_packet_fec_frame_host(uint8_t *frame /* uint8_t[2472] */, vit_fec_rec *out);
+/* One record per slot of nframes logical frames of framebytes bytes at d_bytes (only read).  Per frame the walk starts
+ * at slot 0: a packet starts there, its length field says where the next one starts, and so on; the walk trusts the
+ * length field whether or not the CRC holds and starts again at the next frame.  One wavefront per 64 / (framebytes/24)
+ * logical frames, a lane per slot. */
+int vit_packets_dev(const uint8_t *d_bytes, uint32_t framebytes, int64_t nframes,
+                    vit_packet_rec *d_rec /* vit_packet_rec[nframes*framebytes/24] */, void *stream);
+
 /* From the FFT: differential demodulation, frequency de-interleaving, QPSK demapping and quantisation of whole
  * transmission frames (EN 300 401 clauses 14.5 - 14.7 seen from the receiver) - the step between an FFT on the device and
  * vit_decode_fic_dev / the ring of the *_ti_dev calls.

@@ -37,6 +37,7 @@ EXPORTS = [
     "vit_ofdm_demap_soft_dev", "vit_ofdm_demod_soft_dev", "vit_ofdm_acquire_dev",
     "vit_ofdm_tii_dev", "vit_tii_pair_bins", "vit_tii_main_id",
     "vit_resample_taps", "vit_resample_out_count", "vit_iq_resample_dev",
+    "vit_packet_fec_sync_dev", "vit_packet_fec_count", "vit_packet_fec_dev", "vit_packet_fec_frame_host", "vit_packets_dev",
     "vit_decode_stream_multi",
 ]
 MULTI_LOOPBACK = 0x1
@@ -58,6 +59,13 @@ DESC_DTYPE = np.dtype([("sym_offset", "<u8"), ("out_offset", "<u8"), ("framebits
 AU_DTYPE = np.dtype([("status", "u1"), ("num_aus", "u1"), ("param", "u1"), ("crc_ok", "u1"), ("au_start", "<u2", (7,)),
                      ("fire_ok", "u1"), ("reserved", "u1")])
 AU_OK, AU_RS_FAILED, AU_BAD_HEADER = 0, 1, 2
+
+# packet mode (include/viterbi_amd.h): vit_fec_rec per FEC frame, vit_packet_rec per 24-byte slot
+FEC_REC_DTYPE = np.dtype([("nerr", "i1", (12,)), ("hdr_ok", "<u2"), ("status", "u1"), ("reserved", "u1")])
+PACKET_REC_DTYPE = np.dtype([("kind", "u1"), ("crc_ok", "u1"), ("nslots", "u1"), ("flags", "u1"), ("address", "<u2"),
+                             ("useful", "u1"), ("reserved", "u1")])
+PKT_CONT, PKT_DATA, PKT_PADDING, PKT_FEC, PKT_OVERRUN = 0, 1, 2, 3, 4
+PKT_SLOT, FEC_FRAME_SLOTS, FEC_FRAME_BYTES = 24, 103, 2472
 
 # vit_ens_subch / vit_ens_layout of include/viterbi_amd.h: one entry per sub-channel of an ensemble, and where its blocks lie
 ENS_MAX_SUBCH = 64
@@ -250,6 +258,12 @@ def lib():
         L.vit_resample_out_count.argtypes = [C.c_uint64, C.POINTER(ResampleParams)]
         L.vit_resample_out_count.restype = C.c_int64
         L.vit_iq_resample_dev.argtypes = [vp, C.c_uint64, pf, C.POINTER(ResampleParams), C.c_int64, vp, C.c_uint64, vp]
+        L.vit_packet_fec_sync_dev.argtypes = [vp, C.c_int64, vp, vp]
+        L.vit_packet_fec_count.argtypes = [C.c_int64, C.c_uint32]
+        L.vit_packet_fec_count.restype = C.c_int64
+        L.vit_packet_fec_dev.argtypes = [vp, vp, C.c_int64, C.c_uint32, vp, vp]
+        L.vit_packet_fec_frame_host.argtypes = [vp, vp]
+        L.vit_packets_dev.argtypes = [vp, C.c_uint32, C.c_int64, vp, vp]
         _lib = L
     return _lib
 
@@ -546,6 +560,43 @@ def fire_code_dev(d_bytes, stride, n, d_ok, stream=None):
     """d_ok[i] = the fire code of the 11 bytes at d_bytes + i*stride (stride 24*RSDims over descrambled frames: every
     logical frame as a candidate superframe start)"""
     _check(lib().vit_fire_code_dev(_ptr(d_bytes), stride, n, _ptr(d_ok), _stream_ptr(stream)), "vit_fire_code_dev")
+
+
+def packet_fec_sync_dev(d_stream, nslots, d_score, stream=None):
+    """d_score (103 uint32 on the device) [p] = how many slots of the stream carry the FEC packet header that phase p puts
+    there; the phase of the FEC frames is the largest score's"""
+    _check(lib().vit_packet_fec_sync_dev(_ptr(d_stream), nslots, _ptr(d_score), _stream_ptr(stream)), "vit_packet_fec_sync_dev")
+
+
+def packet_fec_count(nslots, phase):
+    """whole FEC frames in nslots slots from `phase` on"""
+    n = int(lib().vit_packet_fec_count(nslots, phase))
+    if n < 0:
+        raise ViterbiError("vit_packet_fec_count failed: " + last_error())
+    return n
+
+
+def packet_fec_dev(d_stream, d_out, nslots, phase, d_fec, stream=None):
+    """RS(204,188) over the packet_fec_count(nslots, phase) whole FEC frames of the stream (uint8 CUDA tensors; d_out is
+    d_stream or does not overlap it); one FEC_REC_DTYPE record (16 bytes, in the uint8 tensor d_fec) per frame"""
+    _check(lib().vit_packet_fec_dev(_ptr(d_stream), _ptr(d_out), nslots, phase, _ptr(d_fec), _stream_ptr(stream)),
+           "vit_packet_fec_dev")
+
+
+def packet_fec_frame_host(frame):
+    """host, no GPU: one FEC frame of 2472 bytes -> (the decoded frame, its FEC_REC_DTYPE record)"""
+    frame = np.array(frame, np.uint8).reshape(-1)
+    if frame.size != FEC_FRAME_BYTES:
+        raise ValueError("an FEC frame has 2472 bytes")
+    out = np.zeros(1, FEC_REC_DTYPE)
+    _check(lib().vit_packet_fec_frame_host(_np(frame), _np(out)), "vit_packet_fec_frame_host")
+    return frame, out[0]
+
+
+def packets_dev(d_bytes, framebytes, nframes, d_rec, stream=None):
+    """one PACKET_REC_DTYPE record (8 bytes, in the uint8 tensor d_rec) per 24-byte slot of nframes logical frames of
+    framebytes bytes"""
+    _check(lib().vit_packets_dev(_ptr(d_bytes), framebytes, nframes, _ptr(d_rec), _stream_ptr(stream)), "vit_packets_dev")
 
 
 def cif_ring(d_ring, first_row):

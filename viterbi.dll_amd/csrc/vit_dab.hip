@@ -16,6 +16,7 @@
 //
 // FIBs: one lane per 32-byte FIB.  It loads the FIB once, XORs the PRBS bytes of its position in the frame, stores
 // it back, runs a byte-table CRC (256 x u32 in LDS) over bytes 0..29 and writes its flag.
+#include "vit_crc_dev.h"
 #include "vit_internal.h"
 
 namespace {
@@ -215,12 +216,7 @@ __global__ __launch_bounds__(TPB) void vit_fib_kernel(uint8_t* __restrict__ fibs
 }
 
 // ---- DAB+ access units (TS 102 563 clause 5.2): superframe header, AU CRCs ---------------------------------------
-// CRC-16 0x1021 over one byte without a table: crc * x^8 + b * x^16 mod g
-__host__ __device__ constexpr u32 crc16_step(u32 crc, u32 b) {
-    u32 x = ((crc >> 8) ^ b) & 0xFFu;
-    x ^= x >> 4;
-    return ((crc << 8) ^ (x << 12) ^ (x << 5) ^ x) & 0xFFFFu;
-}
+// crc16_step (vit_crc_dev.h): CRC-16 0x1021 over one byte without a table
 static_assert(crc16_step(0, 1) == crc16_byte(1) && crc16_step(0, 0xA7) == crc16_byte(0xA7) && crc16_step(0x1234, 0) ==
               (crc16_byte(0x12) ^ 0x3400u), "the table-less byte step is the table's");
 

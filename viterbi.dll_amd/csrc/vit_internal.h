@@ -154,6 +154,15 @@ hipError_t vit_launch_aus(const uint8_t* d_sf, uint64_t sf_stride, uint32_t rsdi
 void vit_au_table_host(const uint8_t* h_sf, uint32_t rsdims, vit_au_table* h_out);
 // d_ok[i] = the fire code of the 11 bytes at d_bytes + i*stride.
 hipError_t vit_launch_fire(const uint8_t* d_bytes, uint64_t stride, int64_t n, uint8_t* d_ok, hipStream_t stream);
+// Packet mode (vit_packet.hip); the caller has checked every argument rule.  vit_launch_fec_sync clears d_score (a memset
+// on the stream) in front of its kernel; vit_launch_fec with d_out != d_stream launches even without a whole frame, for
+// the copy; the host form takes one FEC frame of 2472 bytes.
+hipError_t vit_launch_fec_sync(const uint8_t* d_stream, int64_t nslots, uint32_t* d_score, hipStream_t stream);
+hipError_t vit_launch_fec(const uint8_t* d_stream, uint8_t* d_out, int64_t nslots, uint32_t phase, int64_t nfec, vit_fec_rec* d_fec,
+                          hipStream_t stream);
+void vit_fec_frame_host(uint8_t* frame, vit_fec_rec* h_out);
+hipError_t vit_launch_packets(const uint8_t* d_bytes, uint32_t framebytes, int64_t nframes, vit_packet_rec* d_rec,
+                              hipStream_t stream);
 // RS(120,110) superframe check, one lane per column.
 // host_polls_ret (nsf == 1, rsdims <= 256): d_ret is host-visible and receives its value with system-scope release
 // semantics after the last output byte, so the host may spin on it instead of synchronising the stream.
