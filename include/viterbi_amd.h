@@ -513,6 +513,96 @@ int vit_packet_fec_frame_host(uint8_t *frame /* uint8_t[2472] */, vit_fec_rec *o
 int vit_packets_dev(const uint8_t *d_bytes, uint32_t framebytes, int64_t nframes,
                     vit_packet_rec *d_rec /* vit_packet_rec[nframes*framebytes/24] */, void *stream);
 
+/* Multiplex configuration: from the FIBs that vit_decode_fic_dev leaves on the device to the sub-channel table that
+ * vit_ensemble_dev takes - FIG 0/0 (ensemble identifier, CIF counter), FIG 0/1 (sub-channel organisation) and FIG 0/2
+ * (which sub-channel carries which service component) of EN 300 401 clause 6, and the equal error protection profiles
+ * of clause 11.3.2.  The definitions below are the library's, written without the standard's text at hand; they are
+ * what these calls promise and what the tests check.  Each constant stands once in csrc/vit_fig_fmt.h.
+ * Input: nfibs FIBs of 32 bytes back to back, the layout of d_fibs of vit_decode_fic_dev, at any alignment; only bytes
+ * 0..29 of a FIB are parsed.  d_fib_ok[i] are the flags of vit_decode_fic_dev: a FIB whose flag is 0 is not looked at;
+ * NULL means every FIB is used.  Group g holds the FIBs g*G ... min((g+1)*G, nfibs)-1, G = 1 ... 4096; there are
+ * ngroups = ceil(nfibs/G) groups (G = 12: one mode-I transmission frame a group).
+ *
+ * The walk of one used FIB b[0..29]: position p = 0; while p < 30:
+ *   h = b[p]; h == 0xFF ends the FIB.  type = h>>5, len = h&31.  If p+1+len > 30 the FIB is `malformed` and ends here.
+ *   If type == 0 and len >= 1, the FIG body b[p+1 .. p+len] is examined as below.  In every case p += 1+len (len == 0
+ *   advances one byte).
+ * FIG type 0: t = b[p+1] holds C/N t>>7, OE (t>>6)&1, P/D (t>>5)&1 and the extension t&31.  Only extensions 0, 1 and 2
+ * are read.  One of them with C/N or OE set (the next configuration, another ensemble) counts into n_next and is
+ * otherwise passed over; status bits 2..4 are set by the others, whatever they turn out to hold.  Entries follow from
+ * q = p+2 and end before e = p+1+len.
+ *   extension 0   needs e-q >= 4, else `malformed`: EId b[q]<<8|b[q+1], change flags b[q+2]>>6, Al (b[q+2]>>5)&1, cif
+ *                 (b[q+2]&31)<<8|b[q+3]; a fifth byte is ignored.
+ *   extension 1   while q < e: fewer than 3 bytes left is `malformed` and ends the FIG.  SubChId b[q]>>2, start
+ *                 (b[q]&3)<<8|b[q+1].  b[q+2]>>7 == 0, short form: table switch (b[q+2]>>6)&1, table index b[q+2]&63, 3
+ *                 bytes.  b[q+2]>>7 == 1, long form: a missing 4th byte is `malformed` and ends the FIG; option
+ *                 (b[q+2]>>4)&7, level (b[q+2]>>2)&3, size (b[q+2]&3)<<8|b[q+3], 4 bytes.
+ *   extension 2   while q < e: a service identifier of 2 bytes (P/D 0) or 4 bytes (P/D 1), big-endian; one byte whose
+ *                 low 4 bits are the component count nc; nc components of 2 bytes c0 c1 with TMId c0>>6.  TMId 0 and 1:
+ *                 type c0&63, SubChId c1>>2, P/S (c1>>1)&1, CA c1&1 - one component entry.  TMId 2 and 3 give none.  If
+ *                 the identifier with its count byte, or any of the nc components, does not fit before e, the FIG is
+ *                 `malformed` and ends there; the components read before still count.
+ * Packed words:
+ *   org    bit 31 present, bit 30 long form, bits 9..0 start; long: bits 19..10 size, 21..20 level, 24..22 option;
+ *          short: bits 15..10 table index, bit 16 table switch; other bits 0
+ *   comp   bit 31 present, bits 1..0 TMId, bits 7..2 type, bit 8 P/S, bit 9 CA; other bits 0
+ * Per group the entries are ordered by (FIB index, byte offset in the FIB), and the last entry for a SubChId wins - for
+ * org and for (comp, sid) separately.  The result does not depend on scheduling: two runs give the same bytes.
+ * A FIB holds at most 12 entries (a component costs 2 bytes behind 5 bytes of headers; a sub-channel 3, a FIG 0/0 six)
+ * and at most 15 FIGs, so with G <= 4096 every count below stays inside 16 bits (49152, 61440). */
+typedef struct vit_mci_subch {      /* 20 bytes; d_sub[g*64 + SubChId]; written completely, all 0 if never signalled */
+    uint32_t org, comp, sid;
+    uint16_t n_org, n_org_other;    /* FIG 0/1 entries of the group for this SubChId equal to / different from org */
+    uint16_t n_comp, n_comp_other;  /* FIG 0/2 entries equal to / different from (comp, sid) */
+} vit_mci_subch;
+typedef struct vit_mci_group {      /* 16 bytes; written completely */
+    uint16_t eid, cif;              /* of the last FIG 0/0 of the group */
+    uint8_t  flags, reserved;       /* bit 0: a FIG 0/0 was seen, bits 2..1 change flags, bit 3 Al */
+    uint16_t nfib_used, nfib_malformed;
+    uint16_t n_ens_other;           /* FIG 0/0 entries whose (eid, change, Al) differ from the last one's */
+    uint16_t n_next, reserved2;     /* FIGs 0/0..0/2 passed over for C/N or OE */
+} vit_mci_group;
+#define VIT_MCI_USED      0x01      /* d_status[i]: the FIB was walked (a FIB that is not used gets 0) */
+#define VIT_MCI_MALFORMED 0x02
+#define VIT_MCI_FIG00     0x04      /* a FIG 0/0, 0/1, 0/2 of the current configuration was read */
+#define VIT_MCI_FIG01     0x08
+#define VIT_MCI_FIG02     0x10
+/* d_sub receives 64*ngroups records, d_grp ngroups, d_status (may be NULL) nfibs bytes.  Errors as the other *_dev
+ * calls: VIT_ERR_NO_DEVICE first; VIT_ERR_ARG with vit_last_error() for a NULL d_fibs, d_sub or d_grp, G outside
+ * 1 ... 4096, a negative nfibs, or a d_sub / d_grp that is not 4-byte aligned.  nfibs == 0 returns VIT_OK and writes
+ * nothing.  Everything is enqueued on `stream` without synchronising; d_fibs is only read, and no byte outside its
+ * 32*nfibs bytes.  One launch: a wavefront per group for G <= 64, a workgroup per group over tiles of 256 FIBs above. */
+int vit_mci_fibs_dev(const uint8_t *d_fibs, const uint8_t *d_fib_ok /* may be NULL */, int64_t nfibs, uint32_t G,
+                     vit_mci_subch *d_sub, vit_mci_group *d_grp, uint8_t *d_status /* may be NULL */, void *stream);
+/* Host only, needs no GPU: the same definition on host memory (no alignment rule; otherwise the same VIT_ERR_ARG). */
+int vit_mci_fibs_host(const uint8_t *h_fibs, const uint8_t *h_fib_ok, int64_t nfibs, uint32_t G,
+                      vit_mci_subch *h_sub, vit_mci_group *h_grp, uint8_t *h_status);
+/* Host only: the profile of an EEP (long form) sub-channel of size_cu capacity units.  The library still compiles in no
+ * puncturing vectors: keep_pi[i] is the caller's vector PI_(i+1) as a keep mask (see "Punctured input"), which must have
+ * 8+i+1 one bits, and keep_tail the tail's, 12 one bits in its low 24 and none above; otherwise VIT_ERR_ARG.
+ * Built-in rule, L counted in blocks of 32 trellis steps (128 mother-code bits):
+ *   option 0 (A)  n = size_cu/12, /8, /6, /4 for level 0 ... 3; framebits = 192n; (L1, L2, PI1, PI2) =
+ *                 level 0 (6n-3, 3, 24, 23); level 1 (5, 1, 13, 12) for n = 1, else (2n-3, 4n+3, 14, 13);
+ *                 level 2 (6n-3, 3, 8, 7); level 3 (4n-3, 2n+3, 3, 2)
+ *   option 1 (B)  n = size_cu/27, /21, /18, /15; framebits = 768n; L1 = 24n-3, L2 = 3; (PI1, PI2) = (10, 9), (6, 5),
+ *                 (4, 3), (2, 1)
+ * out receives the three segments {32*L1, PI1}, {32*L2, PI2}, {6, keep_tail}, *framebits the frame length.  VIT_ERR_ARG
+ * also for a NULL pointer, option > 1, level > 3, a size_cu that is not a positive multiple of the unit, or framebits >
+ * 9216.  Every result satisfies vit_punctured_length(out, *framebits) == 64*size_cu. */
+int vit_eep_profile(uint32_t option, uint32_t level, uint32_t size_cu, const uint32_t keep_pi[24], uint32_t keep_tail,
+                    vit_punct_profile *out, uint32_t *framebits);
+/* Host only: the 64 records of one group -> rows for vit_ensemble_dev, SubChIds in ascending order.  A SubChId whose org
+ * is present in long form, whose EEP profile builds (vit_eep_profile) and whose comp is present gives one row: col =
+ * 64*start, framebits, nsym = 64*size, RSDims = framebits/192 if TMId 0 and type 63 (DAB+) else 0, profile = its index in
+ * h_profiles (identical profiles are stored once), phase = nframes = reserved = 0 - superframe phase and batch length
+ * stay the caller's, who fills them before vit_ensemble_layout.  Every other SubChId whose org is present - short form,
+ * option > 1, a size the rule rejects, no component - sets bit SubChId of *skipped.  h_out has room for 64 rows, *nsub
+ * receives their number; *nprofiles is the capacity of h_profiles going in and the number stored coming out.
+ * VIT_ERR_ARG for a NULL pointer, vectors that vit_eep_profile rejects, or a capacity that is too small. */
+int vit_mci_ens_table(const vit_mci_subch h_sub[64], const uint32_t keep_pi[24], uint32_t keep_tail,
+                      vit_ens_subch *h_out, uint32_t *nsub, vit_punct_profile *h_profiles, uint32_t *nprofiles,
+                      uint64_t *skipped);
+
 /* From the FFT: differential demodulation, frequency de-interleaving, QPSK demapping and quantisation of whole
  * transmission frames (EN 300 401 clauses 14.5 - 14.7 seen from the receiver) - the step between an FFT on the device and
  * vit_decode_fic_dev / the ring of the *_ti_dev calls.

@@ -38,6 +38,7 @@ EXPORTS = [
     "vit_ofdm_tii_dev", "vit_tii_pair_bins", "vit_tii_main_id",
     "vit_resample_taps", "vit_resample_out_count", "vit_iq_resample_dev",
     "vit_packet_fec_sync_dev", "vit_packet_fec_count", "vit_packet_fec_dev", "vit_packet_fec_frame_host", "vit_packets_dev",
+    "vit_mci_fibs_dev", "vit_mci_fibs_host", "vit_eep_profile", "vit_mci_ens_table",
     "vit_decode_stream_multi",
 ]
 MULTI_LOOPBACK = 0x1
@@ -66,6 +67,14 @@ PACKET_REC_DTYPE = np.dtype([("kind", "u1"), ("crc_ok", "u1"), ("nslots", "u1"),
                              ("useful", "u1"), ("reserved", "u1")])
 PKT_CONT, PKT_DATA, PKT_PADDING, PKT_FEC, PKT_OVERRUN = 0, 1, 2, 3, 4
 PKT_SLOT, FEC_FRAME_SLOTS, FEC_FRAME_BYTES = 24, 103, 2472
+
+# multiplex configuration (include/viterbi_amd.h): vit_mci_subch per (group, SubChId), vit_mci_group per group
+MCI_SUBCH_DTYPE = np.dtype([("org", "<u4"), ("comp", "<u4"), ("sid", "<u4"), ("n_org", "<u2"), ("n_org_other", "<u2"),
+                            ("n_comp", "<u2"), ("n_comp_other", "<u2")])
+MCI_GROUP_DTYPE = np.dtype([("eid", "<u2"), ("cif", "<u2"), ("flags", "u1"), ("reserved", "u1"), ("nfib_used", "<u2"),
+                            ("nfib_malformed", "<u2"), ("n_ens_other", "<u2"), ("n_next", "<u2"), ("reserved2", "<u2")])
+MCI_USED, MCI_MALFORMED, MCI_FIG00, MCI_FIG01, MCI_FIG02 = 1, 2, 4, 8, 16
+MCI_MAX_G = 4096
 
 # vit_ens_subch / vit_ens_layout of include/viterbi_amd.h: one entry per sub-channel of an ensemble, and where its blocks lie
 ENS_MAX_SUBCH = 64
@@ -264,6 +273,10 @@ def lib():
         L.vit_packet_fec_dev.argtypes = [vp, vp, C.c_int64, C.c_uint32, vp, vp]
         L.vit_packet_fec_frame_host.argtypes = [vp, vp]
         L.vit_packets_dev.argtypes = [vp, C.c_uint32, C.c_int64, vp, vp]
+        L.vit_mci_fibs_dev.argtypes = [vp, vp, C.c_int64, C.c_uint32, vp, vp, vp, vp]
+        L.vit_mci_fibs_host.argtypes = [vp, vp, C.c_int64, C.c_uint32, vp, vp, vp]
+        L.vit_eep_profile.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, pp, vp]
+        L.vit_mci_ens_table.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -597,6 +610,61 @@ def packets_dev(d_bytes, framebytes, nframes, d_rec, stream=None):
     """one PACKET_REC_DTYPE record (8 bytes, in the uint8 tensor d_rec) per 24-byte slot of nframes logical frames of
     framebytes bytes"""
     _check(lib().vit_packets_dev(_ptr(d_bytes), framebytes, nframes, _ptr(d_rec), _stream_ptr(stream)), "vit_packets_dev")
+
+
+def mci_fibs_dev(d_fibs, nfibs, G, d_sub, d_grp, d_fib_ok=None, d_status=None, stream=None):
+    """FIG 0/0, 0/1 and 0/2 of nfibs 32-byte FIBs (uint8 CUDA tensors; d_fib_ok: the flags of decode_fic_dev, None = every
+    FIB is used), resolved per group of G FIBs: 64 MCI_SUBCH_DTYPE records (20 bytes each, in the uint8 tensor d_sub) and
+    one MCI_GROUP_DTYPE record (16 bytes, in d_grp) per group; d_status: one byte per FIB, optional"""
+    _check(lib().vit_mci_fibs_dev(_ptr(d_fibs), _ptr(d_fib_ok), nfibs, G, _ptr(d_sub), _ptr(d_grp), _ptr(d_status),
+                                  _stream_ptr(stream)), "vit_mci_fibs_dev")
+
+
+def mci_fibs_host(fibs, G, fib_ok=None):
+    """host, no GPU: the same definition -> (MCI_SUBCH_DTYPE array (ngroups, 64), MCI_GROUP_DTYPE array (ngroups,), the
+    status bytes)"""
+    fibs = np.ascontiguousarray(fibs, np.uint8).reshape(-1, 32)
+    n = fibs.shape[0]
+    ng = (n + G - 1) // G if 1 <= G <= MCI_MAX_G else 0
+    sub, grp, st = np.zeros((ng, 64), MCI_SUBCH_DTYPE), np.zeros(ng, MCI_GROUP_DTYPE), np.zeros(n, np.uint8)
+    ok = None if fib_ok is None else np.ascontiguousarray(fib_ok, np.uint8).reshape(n)
+    _check(lib().vit_mci_fibs_host(_np(fibs), None if ok is None else _np(ok), n, G, _np(sub), _np(grp), _np(st)),
+           "vit_mci_fibs_host")
+    return sub, grp, st
+
+
+def _keep_vectors(keep_pi):
+    """24 puncturing vectors PI_1 ... PI_24 (ints, or '0'/'1' strings as for punct_profile) -> uint32 array"""
+    v = [punct_profile([(8, k)]).seg[0].keep for k in keep_pi]
+    if len(v) != 24:
+        raise ValueError("keep_pi holds the 24 vectors PI_1 ... PI_24")
+    return np.array(v, np.uint32)
+
+
+def eep_profile(option, level, size_cu, keep_pi, keep_tail):
+    """host, no GPU: the EEP profile of a long-form sub-channel (option 0 = A, 1 = B; level 0 ... 3) of size_cu capacity
+    units from the caller's vectors -> (PunctProfile, framebits); ViterbiError where the rule has no such profile"""
+    pi = _keep_vectors(keep_pi)
+    tail = punct_profile([(6, keep_tail)]).seg[0].keep
+    out, fb = PunctProfile(), C.c_uint32(0)
+    _check(lib().vit_eep_profile(option, level, size_cu, _np(pi), tail, C.byref(out), C.byref(fb)), "vit_eep_profile")
+    return out, int(fb.value)
+
+
+def mci_ens_table(sub, keep_pi, keep_tail, max_profiles=64):
+    """host, no GPU: one group's 64 MCI_SUBCH_DTYPE records -> (ENS_SUBCH_DTYPE rows for ensemble_dev with phase and
+    nframes still 0, the list of their PunctProfile, the mask of SubChIds that are signalled but give no row)"""
+    sub = np.ascontiguousarray(np.asarray(sub, MCI_SUBCH_DTYPE).reshape(-1))
+    if sub.size != 64:
+        raise ValueError("a group has 64 records")
+    pi = _keep_vectors(keep_pi)
+    tail = punct_profile([(6, keep_tail)]).seg[0].keep
+    rows = np.zeros(64, ENS_SUBCH_DTYPE)
+    profs = (PunctProfile * max(max_profiles, 1))()
+    nsub, nprof, skipped = C.c_uint32(0), C.c_uint32(max_profiles), C.c_uint64(0)
+    _check(lib().vit_mci_ens_table(_np(sub), _np(pi), tail, _np(rows), C.byref(nsub), C.byref(profs), C.byref(nprof),
+                                   C.byref(skipped)), "vit_mci_ens_table")
+    return rows[:nsub.value].copy(), [profs[k] for k in range(nprof.value)], int(skipped.value)
 
 
 def cif_ring(d_ring, first_row):

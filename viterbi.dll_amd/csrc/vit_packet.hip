@@ -26,6 +26,7 @@
 // and none twice - and the lanes that found a root evaluate Forney's formula there and patch the byte in LDS.
 #include "rs_dev.h"
 #include "vit_crc_dev.h"
+#include "vit_image_dev.h"
 #include "vit_packet_fmt.h"
 
 namespace {
@@ -40,24 +41,6 @@ constexpr u32 WPB = TPB / WAVE;
 unsigned grid_for(long long items, u32 per_block) {
     const long long b = (items + per_block - 1) / per_block;
     return (unsigned)(b < (1 << 20) ? b : (1 << 20));
-}
-
-// n bytes at p into an LDS image that keeps p's phase in 16 bytes: byte k at s[(p & 15) + k].  `nthreads` threads call
-// it with t = 0 ... nthreads-1.
-__device__ __forceinline__ void load_image(const uint8_t* p, u32 n, uint8_t* s, u32 t, u32 nthreads) {
-    const u32 a = (u32)(reinterpret_cast<uintptr_t>(p) & 15u);
-    const u32 nwin = (a + n + 15u) >> 4;
-    for (u32 w = t; w < nwin; w += nthreads) {
-        const int o = (int)(16u * w) - (int)a;
-        if (o >= 0 && (u32)o + 16u <= n) {
-            *reinterpret_cast<uint4*>(s + 16u * w) = *reinterpret_cast<const uint4*>(p + o);
-        } else {
-            for (u32 j = 0; j < 16u; j++) {
-                const int k = o + (int)j;
-                if (k >= 0 && (u32)k < n) s[16u * w + j] = p[k];
-            }
-        }
-    }
 }
 
 // ---- packets ------------------------------------------------------------------------------------------------------------
