@@ -1,8 +1,9 @@
 // rs_dev.h -- the device code the RS(120,110) kernels share (rs_kernels.hip: the uniform batch; rs_table.hip: a table of
 // sub-channels): the field's tables, the correction path behind the syndromes (rs_correct), the two front ends
-// (decode_rs, decode_rs_lfsr) and the copies between global memory and LDS.  rs_kernels.hip describes the method.  Each
-// unit includes it into its own unnamed namespace and so keeps its own copy of the constant tables; a unit per kernel
-// also keeps the compiler's inlining of this code into rs_kernel what it was before rs_table.hip existed.
+// (decode_rs, decode_rs_lfsr), the copies between global memory and LDS, and the one text of a pass of the narrow
+// kernels (rs_stage_tables ... rs_pass_finish, at the end).  rs_kernels.hip describes the method.  Each unit includes it
+// into its own unnamed namespace and so keeps its own copy of the constant tables.  No build switch selects among
+// variants of this code: what rounds 2 and 3 measured and dropped is in profiles/HISTORY.md.
 #pragma once
 #include "vit_internal.h"
 
@@ -15,12 +16,11 @@ constexpr int NCW = 120, NMSG = 110;
 constexpr int RS_THREADS = 256;
 constexpr int ATO_ZERO = 512;   // index form of a zero coefficient where a lookup must give 0: ato[512..767] = 0
 constexpr int ATO_SIZE = 768;
-#ifndef COOP_MAX3
-#define COOP_MAX3 12  /* most columns of degree 3 and above in a wave for the column-at-a-time search chien_wave (wave's largest degree 3 / 4 or 5) */
-#endif
-#ifndef COOP_MAX5
-#define COOP_MAX5 28  /* the stress mix of tests/tools/bench_rs.py holds 20 +- 4 per wave (and ends most superframes early), a mix without failures but 0..5 errors in every column 32 +- 4 */
-#endif
+constexpr int NOFAIL = 0x7FFFFFFF;  // s_minfail of a superframe without an uncorrectable column
+// most columns of degree 3 and above in a wave for the column-at-a-time search chien_wave (wave's largest degree 3 / 4 or 5):
+// the stress mix of tests/tools/bench_rs.py holds 20 +- 4 per wave (and ends most superframes early), a mix without
+// failures but 0..5 errors in every column 32 +- 4
+constexpr int COOP_MAX3 = 12, COOP_MAX5 = 28;
 
 struct GfTables {
     uint8_t ato[ATO_SIZE];  // alpha_to[i % 255] for i < 512 (viterbi.h:101-105), zeros from ATO_ZERO on
@@ -66,13 +66,15 @@ constexpr QuadTable make_quad_table() {
 // different nibbles different banks.  One 256-row table needs one lookup per step instead of two, but 64 random rows
 // cost it ~3x the conflict-free cycles: 0.27 ms per 131072 superframes against 0.18 ms with conflict-free rows
 // (measured with a fake index, profiles/r02_ab_rs_chien.txt), and that loop is LDS-bound.
-#ifndef RS_LFSR2
-#define RS_LFSR2 1  /* two data bytes per LFSR step: four independent lookups, half the dependent chain, 9 instead of 11
-                       instructions per byte (0.195 against 0.201 ms per 131072 clean superframes, profiles/r03_ab_rs_lfsr2.txt) */
-#endif
-constexpr int NIB_TABLES = RS_LFSR2 ? 4 : 2;
+// g_8, g_9 sit in the LAST dword of a row (the third is empty) so that a lookup stays ONE ds_read_b128 (4 LDS cycles per
+// wave): with the payload in the first 12 bytes the compiler narrows it to ds_read_b96, which takes 8 (measured with one
+// byte per step: 0.36 ms against 0.20 per 131072 superframes of RSDims 24).
+// The LFSR takes two data bytes per step (four independent lookups, half the dependent chain, 9 instead of 11
+// instructions per byte: 0.195 against 0.201 ms per 131072 clean superframes, profiles/r03_ab_rs_lfsr2.txt), so a second
+// pair of tables holds the rows of the step after the next.
+constexpr int NIB_TABLES = 4;
 struct NibTable {
-    uint32_t w[NIB_TABLES * 16 * 4];  // LO rows, then HI rows (RS_LFSR2: then the LO and HI rows of the two-step table)
+    uint32_t w[NIB_TABLES * 16 * 4];  // LO rows, then HI rows, then the LO and HI rows of the two-step table
 };
 constexpr NibTable make_nib_table() {
     const GfTables t = make_tables();
@@ -97,7 +99,6 @@ constexpr NibTable make_nib_table() {
                 G.w[(half * 16 + n) * 4 + (j < 8 ? j / 4 : 3)] |= prod << (8 * (j % 4));  // g_8, g_9 in dword 3
             }
         }
-#if RS_LFSR2
     // Two steps at once: r'' = shift2(r; d1, d2) + Row(r_8) + Row2(r_9) with Row2(a)_j = a * (g_(j-1) + g_9 * g_j), g_(-1) = 0
     // (the second step's feedback byte is r_8 + r_9 * g_9, and Row is linear)
     for (int half = 0; half < 2; half++)
@@ -110,7 +111,6 @@ constexpr NibTable make_nib_table() {
                 G.w[((2 + half) * 16 + n) * 4 + (j < 8 ? j / 4 : 3)] |= prod << (8 * (j % 4));
             }
         }
-#endif
     return G;
 }
 __constant__ NibTable g_nib = make_nib_table();
@@ -496,9 +496,9 @@ __device__ int decode_rs(bool active, uint32_t sfid, uint8_t* cw, uint32_t tid, 
 
 // Natural-layout front end (codeword byte k at cwbase[coloff + k * stride]): remainder modulo g(x) by LFSR,
 // r <- r*x + d_k - r_9*(x^10 + g(x)): two conflict-free 16-byte lookups (low and high nibble of the feedback byte,
-// see NibTable) per data byte; two bytes per trip (RS_LFSR2: the second feedback byte is linear in r_8 and r_9, so its
-// row is folded into a second pair of tables and all four lookups of a trip start from the same register).  Called by all lanes; the ones without a column (active == false) walk a valid one
-// and drop the result.
+// see NibTable) per data byte; two bytes per trip (the second feedback byte is linear in r_8 and r_9, so its row is
+// folded into a second pair of tables and all four lookups of a trip start from the same register).  Called by all
+// lanes; the ones without a column (active == false) walk a valid one and drop the result.
 __device__ int decode_rs_lfsr(bool active, uint32_t sfid, uint8_t* cwbase, uint32_t coloff, uint32_t stride,
                               const uint8_t* __restrict__ ato, const uint8_t* __restrict__ iof,
                               const uint8_t* __restrict__ qsol, const uint32_t* __restrict__ gnib,
@@ -506,7 +506,6 @@ __device__ int decode_rs_lfsr(bool active, uint32_t sfid, uint8_t* cwbase, uint3
     uint32_t r0 = 0, r1 = 0, r2 = 0;  // coefficient r_j = byte j of the 80-bit register (r2 above bit 15: junk)
     const uint8_t* q = cwbase + coloff;
     const uint32_t nibbase = (uint32_t)(uintptr_t)(const LDS uint32_t*)gnib;  // LDS byte address
-#if RS_LFSR2
     static_assert(NCW % 2 == 0, "two data bytes per step");
 #pragma unroll 4
     for (int k = 0; k < NCW; k += 2, q += 2 * stride) {
@@ -519,34 +518,10 @@ __device__ int decode_rs_lfsr(bool active, uint32_t sfid, uint8_t* cwbase, uint3
         r2 = xor3(xor3(__builtin_amdgcn_alignbit(r2, r1, 16), lo1.w, hi1.w), lo2.w, hi2.w);
         r1 = xor3(xor3(__builtin_amdgcn_alignbit(r1, r0, 16), lo1.y, hi1.y), lo2.y, hi2.y);
         r0 = xor3(xor3((((r0 << 16) | d2) | (d1 << 8)), lo1.x, hi1.x), lo2.x, hi2.x);
+        // keep the rows' empty dwords (see NibTable) in registers until the rows have arrived: reused for the next
+        // address they would put a wait for the lookup in front of its computation
         asm volatile("" ::"v"(lo1.z), "v"(hi1.z), "v"(lo2.z), "v"(hi2.z));
     }
-#else
-#pragma unroll 8
-    for (int k = 0; k < NCW; k++, q += stride) {
-#ifdef RS_DIAG_NO_DATA
-        const uint32_t d = (uint32_t)k;  // timing-only diagnostic: no data byte read (outputs wrong)
-#else
-        const uint32_t d = *q;
-#endif
-#ifdef RS_DIAG_FAKE_IDX
-        const uint32_t f4 = (uint32_t)k << 4;  // timing-only diagnostic: every lane reads the same rows (outputs wrong)
-#else
-        const uint32_t f4 = r2 >> 4;  // bits 4..11 = r_9
-#endif
-        // g_8, g_9 sit in the LAST dword of a row (the third is empty) so that the access stays ONE ds_read_b128
-        // (4 LDS cycles per wave): with the payload in the first 12 bytes the compiler narrows it to ds_read_b96,
-        // which takes 8 (measured: 0.36 ms against 0.20 per 131072 superframes of RSDims 24)
-        const u32x4 lo = *reinterpret_cast<const LDS u32x4*>(nibbase + (f4 & 0xF0u));
-        const u32x4 hi = *reinterpret_cast<const LDS u32x4*>(nibbase + 256u + ((f4 >> 4) & 0xF0u));
-        r2 = xor3(__builtin_amdgcn_alignbit(r2, r1, 24), lo.w, hi.w);
-        r1 = xor3(__builtin_amdgcn_alignbit(r1, r0, 24), lo.y, hi.y);
-        r0 = xor3((r0 << 8) | d, lo.x, hi.x);
-        // keep the empty dwords' registers allocated until the rows have arrived: reused for the next address they
-        // would put a wait for the lookup in front of its computation
-        asm volatile("" ::"v"(lo.z), "v"(hi.z));
-    }
-#endif
     r2 &= 0xFFFFu;
     const bool err = active && (r0 | r1 | r2) != 0;
     if (!__any(err)) return 0;
@@ -600,13 +575,131 @@ __device__ __forceinline__ void copy_out(uint8_t* dst0, const uint8_t* cw, const
     const uint32_t wps = out_sz / (uint32_t)sizeof(V);
     uint32_t l = tid / wps, o = tid - l * wps;
     while (l < nloc) {
-        if (s_minfail[l] == 0x7FFFFFFF)
+        if (s_minfail[l] == NOFAIL)
             reinterpret_cast<V*>(dst0 + l * out_sz)[o] = reinterpret_cast<const V*>(cw + l * in_sz)[o];
         o += RS_THREADS;
         while (o >= wps) {
             o -= wps;
             l++;
         }
+    }
+}
+
+// ---- One pass of the narrow kernels (RSDims <= 256: rs_kernel, rs_table_kernel) ----
+// A pass is the 256 / rsdims superframes (fewer at the end of a run) a workgroup holds in LDS at once, in their natural
+// layout.  The kernels differ in where a pass's width, place and count come from; everything else is below.
+
+// The tables from constant memory into LDS (in front of the kernel's first barrier).
+__device__ __forceinline__ void rs_stage_tables(uint8_t* ato, uint8_t* iof, uint8_t* qsol, uint32_t* gnib, uint32_t* step,
+                                                uint32_t tid) {
+    for (uint32_t i = tid; i < ATO_SIZE; i += RS_THREADS) ato[i] = g_gf.ato[i];
+    iof[tid] = g_gf.iof[tid];
+    qsol[tid] = g_quad.q[tid];
+    if (tid < (uint32_t)NIB_TABLES * 16u * 4u) gnib[tid] = g_nib.w[tid];
+    for (uint32_t i = tid; i < STEP_TERMS * 256u; i += RS_THREADS) step[i] = g_step.w[i];
+}
+
+// The next pass's input block is fetched into registers (8-byte words, 15 per thread) while the current one is decoded,
+// so the HBM latency of the load phase overlaps the LDS-bound decode of the same workgroup.  src: 8-byte aligned, nw
+// words (a pass's size is a multiple of 8).
+constexpr uint32_t RS_PRE = NCW * RS_THREADS / 8u / RS_THREADS;  // 15
+__device__ __forceinline__ void rs_prefetch(uint2 (&pre)[RS_PRE], const uint8_t* src, uint32_t nw, uint32_t tid) {
+#pragma unroll
+    for (uint32_t k = 0; k < RS_PRE; k++) {
+        const uint32_t i = tid + k * RS_THREADS;
+        pre[k] = i < nw ? reinterpret_cast<const uint2*>(src)[i] : make_uint2(0u, 0u);
+    }
+}
+// When its pass begins the words go into cw, and the registers take the workgroup's next pass, if there is one (more).
+// The pass's n bytes lie off bytes behind p, the next one's next_n at next_off.  An input pointer that is not 8-byte
+// aligned (pre_ok == false) has no prefetch: its pass is copied from memory.
+__device__ __forceinline__ void rs_pass_load(uint8_t* cw, uint2 (&pre)[RS_PRE], bool pre_ok, const uint8_t* p, size_t off,
+                                             uint32_t n, bool more, size_t next_off, uint32_t next_n, uint32_t tid) {
+    if (pre_ok) {
+        const uint32_t nw = n / 8u;
+#pragma unroll
+        for (uint32_t k = 0; k < RS_PRE; k++) {
+            const uint32_t i = tid + k * RS_THREADS;
+            if (i < nw) reinterpret_cast<uint2*>(cw)[i] = pre[k];
+        }
+        if (more) rs_prefetch(pre, p + next_off, next_n / 8u, tid);
+    } else {
+        copy_linear(cw, p + off, n, tid);
+    }
+}
+
+__device__ __forceinline__ void rs_pass_reset(int* s_minfail, int* s_sum, uint32_t spb, uint32_t tid) {
+    if (tid < spb) {
+        s_minfail[tid] = NOFAIL;
+        s_sum[tid] = 0;
+    }
+}
+
+// Issue priority that rotates pass by pass (see vit_pk.hip: the hardware's arbitration otherwise lets the waves of a SIMD
+// - here one of each of the CU's four workgroups - advance one after the other): in rs_kernel -3 % on clean data, -6 % with
+// errors in 6 % of the columns (round 3, profiles/r03_ab_rs_lfsr2.txt).  slot: rs_prio_slot() of the wave; pass: how many
+// passes the workgroup has behind it; passes / grid: of the launch.  A launch of one or two passes per workgroup has
+// nothing to level (and measured 2 % slower with it).
+__device__ __forceinline__ uint32_t rs_prio_slot() {
+    uint32_t hwid;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+    return hwid & 3u;
+}
+__device__ __forceinline__ void rs_prio_rotate(uint32_t slot, uint32_t pass, long long passes, uint32_t grid) {
+    if (passes > 2 * (long long)grid)
+        switch ((slot + pass) & 3u) {
+            case 0: __builtin_amdgcn_s_setprio(0); break;
+            case 1: __builtin_amdgcn_s_setprio(1); break;
+            case 2: __builtin_amdgcn_s_setprio(2); break;
+            default: __builtin_amdgcn_s_setprio(3); break;
+        }
+}
+
+// A pass behind its load: cw holds nloc superframes of rsdims columns (in_sz bytes each), s_minfail / s_sum are reset
+// and the barrier behind all that is passed.  Decodes, writes the superframes' out_sz output bytes from dst0 on and
+// their return values from ret0 on.  lsf / colidx: this lane's superframe of the pass and column in it.  Ends in front
+// of the pass's last barrier.
+// polled: the single-call path (RScheckSuperframe), where the host spins on ret[0] in its mapped buffer instead of
+// waiting for the end-of-kernel signal, so every output byte must be visible system-wide before the return value is.
+// The column loops state their unroll count: left to the compiler it was 5 or all 110 rows (1250 instructions more in
+// rs_table_kernel) for the same text, depending on how the callers' address arithmetic had been folded into the loop.
+__device__ __forceinline__ void rs_pass_finish(uint8_t* cw, uint32_t tid, uint32_t rsdims, uint32_t lsf, uint32_t colidx,
+                                               uint32_t in_sz, uint32_t out_sz, uint32_t nloc, uint8_t* dst0, int32_t* ret0,
+                                               bool polled, const uint8_t* ato, const uint8_t* iof, const uint8_t* qsol,
+                                               const uint32_t* gnib, const uint32_t* step, int* s_minfail, int* s_sum) {
+    const bool active = lsf < nloc;
+    const int res = decode_rs_lfsr(active, lsf, cw, active ? lsf * in_sz + colidx : 0u, rsdims, ato, iof, qsol, gnib, step);  // all lanes
+    if (res < 0) atomicMin(&s_minfail[lsf], (int)colidx);
+    __syncthreads();
+    // superframes without a failure: their first 110 rows go out as one linear block each, where that can be done in dwords
+    const bool blocks = (out_sz & 3u) == 0 && (reinterpret_cast<uintptr_t>(dst0) & 3u) == 0;
+    if (blocks) {
+        // 16-byte pieces when the block sizes and the destination allow it (in_sz is a multiple of 8, both are of 16
+        // when rsdims is a multiple of 8), else dwords (the quotient c / wps in every trip of the plain loop was a
+        // quarter of the clean path's instructions)
+        if ((out_sz & 15u) == 0 && (in_sz & 15u) == 0 && (reinterpret_cast<uintptr_t>(dst0) & 15u) == 0)
+            copy_out<uint4>(dst0, cw, s_minfail, nloc, in_sz, out_sz, tid);
+        else
+            copy_out<uint32_t>(dst0, cw, s_minfail, nloc, in_sz, out_sz, tid);
+    }
+    if (active) {
+        const int mf = s_minfail[lsf];
+        if ((int)colidx < mf) {  // columns before the first failure are written, and counted
+            if (!blocks || mf != NOFAIL) {
+                uint8_t* dst = dst0 + (lsf * out_sz + colidx);  // < 110 * 256
+                const uint8_t* src = cw + lsf * in_sz + colidx;
+#pragma clang loop vectorize(disable) interleave(disable) unroll_count(5)
+                for (int k = 0; k < NMSG; k++) dst[(size_t)k * rsdims] = src[k * rsdims];
+            }
+            atomicAdd(&s_sum[lsf], res);
+        }
+    }
+    if (polled) __threadfence_system();
+    __syncthreads();
+    if (tid < nloc) {
+        const int32_t r = s_minfail[tid] != NOFAIL ? -1 : s_sum[tid];
+        if (polled) __hip_atomic_store(&ret0[tid], r, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        else ret0[tid] = r;
     }
 }
 

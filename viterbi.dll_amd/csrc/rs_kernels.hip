@@ -16,6 +16,8 @@
 // entered by a whole wavefront as soon as one of its columns has an error: Berlekamp-Massey on logs,
 // locator roots in closed form (degree 1, 2), a wavefront per column (chien_wave) or four positions per
 // lookup (chien_quad), Forney.  rs_kernel_wide keeps the transposed-LDS form for RSDims > 256.
+// What rs_kernel does with a pass - load, decode, first failure, copy-out, return values - is rs_dev.h's text, shared with
+// rs_table_kernel (rs_table.hip); here is only the uniform arithmetic of a pass's place and the polled return's flag.
 //
 // Replaces, from scratch: RScheckSuperframe (rschecksf.cpp:65-93), DECODE_RS
 // (:199-377), Mod255 (:50-52) and CreateLookupTables (dllmain.cpp:124-146).
@@ -88,10 +90,12 @@ __global__ __launch_bounds__(RS_THREADS) void rs_kernel_wide(const uint8_t* __re
 }
 
 
-// rsdims <= 256: spb = 256/rsdims superframes per pass, natural layout in LDS (see the header comment).
+// rsdims <= 256: spb = 256/rsdims superframes per pass, natural layout in LDS (see the header comment); the pass itself is
+// rs_dev.h's, shared with rs_table_kernel.
 // LDS: 30720 (codewords) + 5120 (Chien steps) + 1024 (LFSR nibble rows) + 768 + 256 + 256 + 2048 = 40192 B: four workgroups
 // share a CU (second launch bound: 4 waves per SIMD); a three-workgroup build was 6 % slower on clean data
 // (profiles/r02_ab_rs_chien.txt).
+constexpr bool RS_KERNEL_ROTATES_PRIO = true;  // rs_prio_rotate: measured here (round 3)
 __global__ __launch_bounds__(RS_THREADS, 4) void rs_kernel(const uint8_t* __restrict__ p, uint8_t* __restrict__ out,
                                                         int32_t* __restrict__ ret, uint32_t rsdims,
                                                         long long nsf, int host_polls_ret) {
@@ -104,130 +108,33 @@ __global__ __launch_bounds__(RS_THREADS, 4) void rs_kernel(const uint8_t* __rest
     __shared__ int s_minfail[RS_THREADS];
     __shared__ int s_sum[RS_THREADS];
     const uint32_t tid = threadIdx.x;
-    for (uint32_t i = tid; i < ATO_SIZE; i += RS_THREADS) ato[i] = g_gf.ato[i];
-    iof[tid] = g_gf.iof[tid];
-    qsol[tid] = g_quad.q[tid];
-    if (tid < (uint32_t)NIB_TABLES * 16u * 4u) gnib[tid] = g_nib.w[tid];
-    for (uint32_t i = tid; i < STEP_TERMS * 256u; i += RS_THREADS) step[i] = g_step.w[i];
+    rs_stage_tables(ato, iof, qsol, gnib, step, tid);
     __syncthreads();
 
     const uint32_t spb = RS_THREADS / rsdims;
     const long long ngroups = (nsf + spb - 1) / spb;
     const uint32_t in_sz = NCW * rsdims, out_sz = NMSG * rsdims;
     const uint32_t lsf = tid / rsdims, colidx = tid - lsf * rsdims;
-    constexpr int NOFAIL = 0x7FFFFFFF;
+    auto count = [&](long long gg) { return nsf - gg * spb < (long long)spb ? (uint32_t)(nsf - gg * spb) : spb; };  // superframes of group gg
 
-    // The next group's input block is fetched into registers (8-byte words, 15 per thread) while the current
-    // one is decoded, so the HBM latency of the load phase overlaps the LDS-bound decode of the same workgroup.
-    constexpr uint32_t PRE = NCW * RS_THREADS / 8u / RS_THREADS;  // 15
     const bool pre_ok = (reinterpret_cast<uintptr_t>(p) & 7u) == 0;  // in_sz is a multiple of 8
-    uint2 pre[PRE];
-    auto prefetch = [&](long long gg) {
-        const long long s0 = gg * spb;
-        const uint32_t nl = nsf - s0 < (long long)spb ? (uint32_t)(nsf - s0) : spb;
-        const uint32_t nw = nl * in_sz / 8u;
-        const uint2* src = reinterpret_cast<const uint2*>(p + (size_t)s0 * in_sz);
-#pragma unroll
-        for (uint32_t k = 0; k < PRE; k++) {
-            const uint32_t i = tid + k * RS_THREADS;
-            pre[k] = i < nw ? src[i] : make_uint2(0u, 0u);
-        }
-    };
-    if (pre_ok && (long long)blockIdx.x < ngroups) prefetch(blockIdx.x);
+    uint2 pre[RS_PRE];
+    if (pre_ok && (long long)blockIdx.x < ngroups)
+        rs_prefetch(pre, p + (size_t)blockIdx.x * spb * in_sz, count(blockIdx.x) * in_sz / 8u, tid);
 
-#ifndef RS_PRIO_ROT
-#define RS_PRIO_ROT 1
-#endif
-#if RS_PRIO_ROT
-    // Issue priority that rotates pass by pass (see vit_pk.hip: the hardware's arbitration otherwise lets the waves of a SIMD - here
-    // one of each of the CU's four workgroups - advance one after the other): -3 % on clean data, -6 % with errors in 6 % of the columns
-    // (profiles/r03_ab_rs_lfsr2.txt).  RS_PRIO_ROT = 2: the four waves of a workgroup share the level (the slot of wave 0).
-    uint32_t rs_slot, rs_pass = 0;
-    {
-        uint32_t hwid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        rs_slot = hwid & 3u;
-#if RS_PRIO_ROT == 2
-        __shared__ uint32_t s_slot;
-        if (tid == 0) s_slot = rs_slot;
-        __syncthreads();
-        rs_slot = s_slot;
-        rs_slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)rs_slot);
-#endif
-    }
-#endif
+    const uint32_t slot = RS_KERNEL_ROTATES_PRIO ? rs_prio_slot() : 0u;
+    uint32_t pass = 0;
     for (long long g = blockIdx.x; g < ngroups; g += gridDim.x) {
-#if RS_PRIO_ROT
-        if (ngroups > 2 * (long long)gridDim.x)  // a launch of one or two passes has nothing to level (and measured 2 % slower with it)
-        switch ((rs_slot + rs_pass) & 3u) {
-            case 0: __builtin_amdgcn_s_setprio(0); break;
-            case 1: __builtin_amdgcn_s_setprio(1); break;
-            case 2: __builtin_amdgcn_s_setprio(2); break;
-            default: __builtin_amdgcn_s_setprio(3); break;
-        }
-        rs_pass++;
-#endif
+        if (RS_KERNEL_ROTATES_PRIO) rs_prio_rotate(slot, pass++, ngroups, gridDim.x);
         const long long sf0 = g * spb;
-        const uint32_t nloc = nsf - sf0 < (long long)spb ? (uint32_t)(nsf - sf0) : spb;
-        if (tid < spb) {
-            s_minfail[tid] = NOFAIL;
-            s_sum[tid] = 0;
-        }
-        if (pre_ok) {
-            const uint32_t nw = nloc * in_sz / 8u;
-#pragma unroll
-            for (uint32_t k = 0; k < PRE; k++) {
-                const uint32_t i = tid + k * RS_THREADS;
-                if (i < nw) reinterpret_cast<uint2*>(cw)[i] = pre[k];
-            }
-            if (g + gridDim.x < ngroups) prefetch(g + gridDim.x);
-        } else {
-            copy_linear(cw, p + (size_t)sf0 * in_sz, nloc * in_sz, tid);
-        }
+        const uint32_t nloc = count(g);
+        rs_pass_reset(s_minfail, s_sum, spb, tid);
+        const long long gn = g + gridDim.x;
+        rs_pass_load(cw, pre, pre_ok, p, (size_t)sf0 * in_sz, nloc * in_sz, gn < ngroups, (size_t)gn * spb * in_sz,
+                     count(gn) * in_sz, tid);
         __syncthreads();
-        const bool active = lsf < nloc;
-        const int res = decode_rs_lfsr(active, lsf, cw, active ? lsf * in_sz + colidx : 0u, rsdims, ato, iof, qsol, gnib, step);  // all lanes
-        if (res < 0) atomicMin(&s_minfail[lsf], (int)colidx);
-        __syncthreads();
-        uint8_t* dst0 = out + (size_t)sf0 * out_sz;
-        // superframes without a failure: their first 110 rows go out as one linear block each
-        if ((out_sz & 3u) == 0 && (reinterpret_cast<uintptr_t>(dst0) & 3u) == 0) {
-            // 16-byte pieces when the block sizes and the destination allow it (in_sz is a multiple of 8, both are of 16
-            // when rsdims is a multiple of 8), else dwords (the quotient c / wps in every trip of the plain loop was a
-            // quarter of the clean path's instructions)
-            if ((out_sz & 15u) == 0 && (in_sz & 15u) == 0 && (reinterpret_cast<uintptr_t>(dst0) & 15u) == 0)
-                copy_out<uint4>(dst0, cw, s_minfail, nloc, in_sz, out_sz, tid);
-            else
-                copy_out<uint32_t>(dst0, cw, s_minfail, nloc, in_sz, out_sz, tid);
-            if (active) {
-                const int mf = s_minfail[lsf];
-                if (mf != NOFAIL && (int)colidx < mf) {  // columns before the first failure are written
-                    uint8_t* dst = dst0 + (lsf * out_sz + colidx);  // < 110 * 256
-                    const uint8_t* src = cw + lsf * in_sz + colidx;
-#pragma clang loop vectorize(disable) interleave(disable)
-                    for (int k = 0; k < NMSG; k++) dst[(size_t)k * rsdims] = src[k * rsdims];
-                }
-                if ((int)colidx < mf) atomicAdd(&s_sum[lsf], res);
-            }
-        } else if (active) {
-            const int mf = s_minfail[lsf];
-            if ((int)colidx < mf) {
-                uint8_t* dst = dst0 + (lsf * out_sz + colidx);  // < 110 * 256
-                const uint8_t* src = cw + lsf * in_sz + colidx;
-#pragma clang loop vectorize(disable) interleave(disable)
-                for (int k = 0; k < NMSG; k++) dst[(size_t)k * rsdims] = src[k * rsdims];
-                atomicAdd(&s_sum[lsf], res);
-            }
-        }
-        // single-call path (RScheckSuperframe): the host spins on ret[0] in its mapped buffer instead of waiting for the
-        // end-of-kernel signal, so every output byte must be visible system-wide before the return value is
-        if (host_polls_ret) __threadfence_system();
-        __syncthreads();
-        if (tid < nloc) {
-            const int32_t r = s_minfail[tid] != NOFAIL ? -1 : s_sum[tid];
-            if (host_polls_ret) __hip_atomic_store(&ret[sf0 + tid], r, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            else ret[sf0 + tid] = r;
-        }
+        rs_pass_finish(cw, tid, rsdims, lsf, colidx, in_sz, out_sz, nloc, out + (size_t)sf0 * out_sz, ret + sf0,
+                       host_polls_ret != 0, ato, iof, qsol, gnib, step, s_minfail, s_sum);
         __syncthreads();
     }
 }
