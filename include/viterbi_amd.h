@@ -512,6 +512,74 @@ int vit_packet_fec_frame_host(uint8_t *frame /* uint8_t[2472] */, vit_fec_rec *o
  * logical frames, a lane per slot. */
 int vit_packets_dev(const uint8_t *d_bytes, uint32_t framebytes, int64_t nframes,
                     vit_packet_rec *d_rec /* vit_packet_rec[nframes*framebytes/24] */, void *stream);
+/* MSC data groups (clause 5.3.3) from the packets: what Slideshow, TPEG, EPG and Journaline decoders consume.  Like the
+ * rest of packet mode these definitions are the library's, written without the standard's text at hand; they are what
+ * these calls promise and what the tests check.
+ * Input: the stream d_bytes, 24*nslots bytes at any alignment, and d_rec, the nslots records that vit_packets_dev wrote
+ * for it (4-byte aligned); both are only read.  Logical frames no longer matter: the records carry what they decided.
+ * 1 <= nslots <= 1<<24; nslots == 0 returns VIT_OK and writes nothing.
+ * Usable packets: slot i is a usable packet if kind == VIT_PKT_DATA, crc_ok == 1 and useful <= 24*nslots_i - 5.  A
+ *   VIT_PKT_DATA slot that fails one of the last two is unusable.  Unusable packets and every other kind take no further
+ *   part.  (Records that vit_packets_dev did not write for this window could claim a packet that ends behind the window's
+ *   last slot or an address above 1023: such a slot is unusable as well, so that no byte outside the stream is read.)  A usable packet's data is bytes 3 ... 3+useful-1 of the packet, its continuity index flags & 3, and it is a
+ *   first / last packet by the bits VIT_PKT_FIRST / VIT_PKT_LAST of flags.
+ * Runs: per address, the usable packets in slot order.  Packet q continues its predecessor p of the same address iff q
+ *   has no first flag, p has no last flag and cont(q) == (cont(p)+1) & 3.  A run is a maximal sequence in which each
+ *   packet continues the one before.
+ * A run is a data group iff its head has the first flag and its tail the last flag (one packet with both is a group).
+ *   It is open iff its head has the first flag, its tail has no last flag and its tail is the address's last usable
+ *   packet of the window.  The packets of every other run are dropped.  (The walk per address - open at a first flag,
+ *   break on a wrong continuity index or a new first flag, close at a last flag - stated free of any order of evaluation.)
+ * Order and layout: groups are numbered k = 0, 1, ... by ascending slot of their last packet.  Group k's bytes D[0..L) are
+ *   the data of its packets in slot order; offset_0 = 0, offset_(k+1) = offset_k + L_k rounded up to a multiple of 16.
+ * Header of a group: L < 2 is malformed.  b0 = D[0]: ext b0>>7, crcf (b0>>6)&1, seg (b0>>5)&1, ua (b0>>4)&1, type b0&15.
+ *   cont_rep = D[1] (continuity index in the high nibble, repetition index in the low).  p = 2, then in this order: if ext,
+ *   p += 2; if seg, segment = D[p]<<8 | D[p+1] (bit 15: last segment), p += 2; if ua, li = D[p]&15, tidf = (D[p]>>4)&1,
+ *   p += 1, a tidf with li < 2 is malformed, a tidf with li >= 2 gives transport_id = D[p]<<8 | D[p+1], then p += li.
+ *   payload_offset = p.  The header is well-formed iff every byte named lies before E = L - (crcf ? 2 : 0) and p <= E.
+ *   A malformed group has flags, segment, transport_id and payload_offset 0 (crc_ok with them) and keeps type and
+ *   cont_rep (0 too if L < 2).  If crcf and well-formed, crc_ok is set when the CRC-16 of D[0..L-2) - 0x1021, preset
+ *   0xFFFF, complemented: the packets' own - equals D[L-2]<<8 | D[L-1]. */
+#define VIT_PKT_LAST  4   /* vit_packet_rec.flags bit 2 */
+#define VIT_PKT_FIRST 8   /* vit_packet_rec.flags bit 3 */
+typedef struct vit_dgroup_rec {      /* 32 bytes per data group, written completely */
+    uint32_t first_slot, last_slot, npackets, offset, length;
+    uint16_t address, segment, transport_id, payload_offset;
+    uint8_t  type, cont_rep,
+             flags,     /* bit 0 well-formed, 1 crcf, 2 crc_ok, 3 seg, 4 ua, 5 tidf, 6 ext */
+             command;   /* the command bit of the first packet */
+} vit_dgroup_rec;
+typedef struct vit_dgroup_summary {  /* 32 bytes, written completely by every call with nslots > 0 */
+    uint32_t ngroups;      /* data groups found */
+    uint32_t nwritten;     /* records written: a prefix */
+    uint32_t data_bytes;   /* offset_ngroups: what d_data must hold for all of them */
+    uint32_t open_from;    /* the smallest first slot of an open run; nslots if there is none */
+    uint32_t n_used, n_dropped, n_unusable;   /* packets: in groups, dropped, unusable */
+    uint32_t reserved;     /* 0 */
+} vit_dgroup_summary;
+/* Group k is written - its record to d_dg[k], its bytes to d_data + offset_k - iff k < max_groups and either d_data is
+ * NULL or offset_k + L_k <= data_capacity; offsets grow, so the written groups are a prefix.  With d_data NULL nothing
+ * is gathered, but header and CRC fields are still computed from the stream (records only).  Bytes of d_data outside
+ * [offset_k, offset_k + L_k) of written groups and records >= nwritten are never written; no byte outside the named
+ * ranges is read.  Enqueued on `stream` without synchronising; the result does not depend on scheduling: two runs give
+ * the same bytes.
+ * Across calls: the call is stateless.  open_from says where the next window must begin for no group to be lost (a
+ * group that was open closes in a window that holds its first packet); groups the caller has seen already come again
+ * in such a window and are recognised by their slots.
+ * Errors: VIT_ERR_NO_DEVICE first; VIT_ERR_ARG with vit_last_error() for nslots outside 0 ... 1<<24 and, with nslots > 0,
+ * for a NULL d_bytes, d_rec or d_sum, a NULL d_dg with max_groups > 0, a d_rec, d_dg or d_sum that is not 4-byte
+ * aligned, or a NULL d_data with data_capacity > 0.
+ * Launches: which addresses have usable packets; a workgroup per such address and chunk of 16384 slots, twice (the state a
+ * chunk hands on, then every closing packet's run); three of a prefix sum over the slots (numbers, offsets, summary); a
+ * wavefront per written group (gather, CRC, header).  Scratch (the calling thread's): 16 bytes per slot, 16 per address
+ * and chunk, 32 per 4096 slots. */
+int vit_data_groups_dev(const uint8_t *d_bytes, const vit_packet_rec *d_rec, int64_t nslots,
+                        vit_dgroup_rec *d_dg, uint32_t max_groups, vit_dgroup_summary *d_sum,
+                        uint8_t *d_data /* may be NULL */, uint32_t data_capacity, void *stream);
+/* Host only, needs no GPU: the same definition on host memory (no alignment rule; otherwise the same VIT_ERR_ARG). */
+int vit_data_groups_host(const uint8_t *bytes, const vit_packet_rec *rec, int64_t nslots,
+                         vit_dgroup_rec *dg, uint32_t max_groups, vit_dgroup_summary *sum,
+                         uint8_t *data /* may be NULL */, uint32_t data_capacity);
 
 /* Multiplex configuration: from the FIBs that vit_decode_fic_dev leaves on the device to the sub-channel table that
  * vit_ensemble_dev takes - FIG 0/0 (ensemble identifier, CIF counter), FIG 0/1 (sub-channel organisation) and FIG 0/2

@@ -38,6 +38,7 @@ EXPORTS = [
     "vit_ofdm_tii_dev", "vit_tii_pair_bins", "vit_tii_main_id",
     "vit_resample_taps", "vit_resample_out_count", "vit_iq_resample_dev",
     "vit_packet_fec_sync_dev", "vit_packet_fec_count", "vit_packet_fec_dev", "vit_packet_fec_frame_host", "vit_packets_dev",
+    "vit_data_groups_dev", "vit_data_groups_host",
     "vit_mci_fibs_dev", "vit_mci_fibs_host", "vit_eep_profile", "vit_mci_ens_table",
     "vit_decode_stream_multi",
 ]
@@ -67,6 +68,19 @@ PACKET_REC_DTYPE = np.dtype([("kind", "u1"), ("crc_ok", "u1"), ("nslots", "u1"),
                              ("useful", "u1"), ("reserved", "u1")])
 PKT_CONT, PKT_DATA, PKT_PADDING, PKT_FEC, PKT_OVERRUN = 0, 1, 2, 3, 4
 PKT_SLOT, FEC_FRAME_SLOTS, FEC_FRAME_BYTES = 24, 103, 2472
+PKT_LAST, PKT_FIRST = 4, 8  # vit_packet_rec.flags
+# MSC data groups: vit_dgroup_rec per group, vit_dgroup_summary per call
+DGROUP_REC_DTYPE = np.dtype([("first_slot", "<u4"), ("last_slot", "<u4"), ("npackets", "<u4"), ("offset", "<u4"), ("length", "<u4"),
+                             ("address", "<u2"), ("segment", "<u2"), ("transport_id", "<u2"), ("payload_offset", "<u2"),
+                             ("type", "u1"), ("cont_rep", "u1"), ("flags", "u1"), ("command", "u1")])
+DGROUP_SUM_DTYPE = np.dtype([("ngroups", "<u4"), ("nwritten", "<u4"), ("data_bytes", "<u4"), ("open_from", "<u4"), ("n_used", "<u4"),
+                             ("n_dropped", "<u4"), ("n_unusable", "<u4"), ("reserved", "<u4")])
+DGF_WELLFORMED, DGF_CRCF, DGF_CRC_OK, DGF_SEG, DGF_UA, DGF_TIDF, DGF_EXT = 1, 2, 4, 8, 16, 32, 64
+DGROUP_MAX_SLOTS = 1 << 24
+# the slot counts at which the kernels of csrc/vit_dgroup.hip change their partition (TILE, CHUNK, NUM_BLOCK, GATHER_STEP
+# there): the link pass's tile and the chunk of one workgroup, the block of the prefix sum, the slots a gathering wavefront
+# takes per step.  Every group is gathered by one wavefront: there is no wavefront/workgroup threshold.
+DGROUP_GEOMETRY = {"link_tile": 1024, "link_chunk": 16384, "number_block": 4096, "gather_step": 64}
 
 # multiplex configuration (include/viterbi_amd.h): vit_mci_subch per (group, SubChId), vit_mci_group per group
 MCI_SUBCH_DTYPE = np.dtype([("org", "<u4"), ("comp", "<u4"), ("sid", "<u4"), ("n_org", "<u2"), ("n_org_other", "<u2"),
@@ -273,6 +287,8 @@ def lib():
         L.vit_packet_fec_dev.argtypes = [vp, vp, C.c_int64, C.c_uint32, vp, vp]
         L.vit_packet_fec_frame_host.argtypes = [vp, vp]
         L.vit_packets_dev.argtypes = [vp, C.c_uint32, C.c_int64, vp, vp]
+        L.vit_data_groups_dev.argtypes = [vp, vp, C.c_int64, vp, C.c_uint32, vp, vp, C.c_uint32, vp]
+        L.vit_data_groups_host.argtypes = [vp, vp, C.c_int64, vp, C.c_uint32, vp, vp, C.c_uint32]
         L.vit_mci_fibs_dev.argtypes = [vp, vp, C.c_int64, C.c_uint32, vp, vp, vp, vp]
         L.vit_mci_fibs_host.argtypes = [vp, vp, C.c_int64, C.c_uint32, vp, vp, vp]
         L.vit_eep_profile.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, pp, vp]
@@ -610,6 +626,29 @@ def packets_dev(d_bytes, framebytes, nframes, d_rec, stream=None):
     """one PACKET_REC_DTYPE record (8 bytes, in the uint8 tensor d_rec) per 24-byte slot of nframes logical frames of
     framebytes bytes"""
     _check(lib().vit_packets_dev(_ptr(d_bytes), framebytes, nframes, _ptr(d_rec), _stream_ptr(stream)), "vit_packets_dev")
+
+
+def data_groups_dev(d_bytes, d_rec, nslots, d_dg, max_groups, d_sum, d_data=None, data_capacity=0, stream=None):
+    """MSC data groups of a stream of nslots slots and the records packets_dev wrote for it (uint8 CUDA tensors): up to
+    max_groups DGROUP_REC_DTYPE records (32 bytes each, in d_dg), one DGROUP_SUM_DTYPE record (32 bytes, in d_sum) and,
+    unless d_data is None (records only), the groups' bytes in d_data, each at its record's offset"""
+    _check(lib().vit_data_groups_dev(_ptr(d_bytes), _ptr(d_rec), nslots, _ptr(d_dg), max_groups, _ptr(d_sum), _ptr(d_data),
+                                     data_capacity, _stream_ptr(stream)), "vit_data_groups_dev")
+
+
+def data_groups_host(stream, rec, max_groups, data_capacity):
+    """host, no GPU: the same definition for a stream (bytes) and its PACKET_REC_DTYPE records -> (the written
+    DGROUP_REC_DTYPE records, the DGROUP_SUM_DTYPE record, the data_capacity bytes of the groups' data with zeros between
+    them); data_capacity None: records only, data is None"""
+    stream = np.ascontiguousarray(stream, np.uint8).reshape(-1)
+    rec = np.ascontiguousarray(rec, PACKET_REC_DTYPE).reshape(-1)
+    if stream.size != PKT_SLOT * rec.size:
+        raise ValueError("one record per 24-byte slot of the stream")
+    dg, summary = np.zeros(max(max_groups, 1), DGROUP_REC_DTYPE), np.zeros(1, DGROUP_SUM_DTYPE)
+    data = None if data_capacity is None else np.zeros(max(data_capacity, 1), np.uint8)
+    _check(lib().vit_data_groups_host(_np(stream), _np(rec), rec.size, _np(dg), max_groups, _np(summary),
+                                      None if data is None else _np(data), data_capacity or 0), "vit_data_groups_host")
+    return dg[:int(summary["nwritten"][0])], summary[0], None if data is None else data[:data_capacity]
 
 
 def mci_fibs_dev(d_fibs, nfibs, G, d_sub, d_grp, d_fib_ok=None, d_status=None, stream=None):

@@ -63,3 +63,43 @@ int vit_packets_dev(const uint8_t* d_bytes, uint32_t framebytes, int64_t nframes
     LAUNCHCHK("packet launch failed: %s", vit_launch_packets(d_bytes, framebytes, nframes, d_rec, (hipStream_t)stream));
     return VIT_OK;
 }
+
+namespace {
+
+// the argument rules that vit_data_groups_dev and vit_data_groups_host share; nullptr if none is broken
+const char* data_groups_why(const void* bytes, const void* rec, int64_t nslots, const void* dg, uint32_t max_groups, const void* sum,
+                            const void* data, uint32_t data_capacity) {
+    if (nslots < 0 || nslots > DG_MAX_SLOTS) return "nslots must be 0 ... 1<<24";
+    if (nslots == 0) return nullptr;  // an empty batch touches no pointer
+    if (!bytes || !rec || !sum) return "NULL bytes, records or summary";
+    if (!dg && max_groups > 0) return "NULL group records with max_groups > 0";
+    if (!data && data_capacity > 0) return "NULL data with data_capacity > 0";
+    return nullptr;
+}
+
+}  // namespace
+
+int vit_data_groups_dev(const uint8_t* d_bytes, const vit_packet_rec* d_rec, int64_t nslots, vit_dgroup_rec* d_dg, uint32_t max_groups,
+                        vit_dgroup_summary* d_sum, uint8_t* d_data, uint32_t data_capacity, void* stream) {
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    const char* why = data_groups_why(d_bytes, d_rec, nslots, d_dg, max_groups, d_sum, d_data, data_capacity);
+    if (!why && nslots > 0 && (misaligned4(d_rec) || misaligned4(d_dg) || misaligned4(d_sum))) why = "d_rec, d_dg and d_sum must be 4-byte aligned";
+    if (why) return bad_arg("vit_data_groups_dev: bad arguments (%s; nslots=%lld max_groups=%u data_capacity=%u)", why, (long long)nslots,
+                            max_groups, data_capacity);
+    if (nslots == 0) return VIT_OK;
+    ScratchLease scratch;
+    const int rc = scratch.begin(vit_data_groups_scratch(nslots), 0, (hipStream_t)stream);
+    if (rc != VIT_OK) return rc;
+    LAUNCHCHK("data group launch failed: %s", vit_launch_data_groups(d_bytes, d_rec, nslots, d_dg, max_groups, d_sum, d_data, data_capacity,
+                                                                     scratch.sym<void>(), (hipStream_t)stream));
+    return scratch.end();
+}
+
+int vit_data_groups_host(const uint8_t* bytes, const vit_packet_rec* rec, int64_t nslots, vit_dgroup_rec* dg, uint32_t max_groups,
+                         vit_dgroup_summary* sum, uint8_t* data, uint32_t data_capacity) {
+    const char* why = data_groups_why(bytes, rec, nslots, dg, max_groups, sum, data, data_capacity);
+    if (why) return bad_arg("vit_data_groups_host: bad arguments (%s; nslots=%lld max_groups=%u data_capacity=%u)", why, (long long)nslots,
+                            max_groups, data_capacity);
+    if (nslots > 0) vit_data_groups_host_impl(bytes, rec, nslots, dg, max_groups, sum, data, data_capacity);
+    return VIT_OK;
+}

@@ -163,6 +163,15 @@ hipError_t vit_launch_fec(const uint8_t* d_stream, uint8_t* d_out, int64_t nslot
 void vit_fec_frame_host(uint8_t* frame, vit_fec_rec* h_out);
 hipError_t vit_launch_packets(const uint8_t* d_bytes, uint32_t framebytes, int64_t nframes, vit_packet_rec* d_rec,
                               hipStream_t stream);
+// Data groups (vit_dgroup.hip); the caller has checked every argument rule.  d_scratch: vit_data_groups_scratch(nslots)
+// bytes, 16-byte aligned; its first 256 bytes are cleared on the stream in front of the kernels.  The host form is the
+// same definition as a walk per address.
+size_t vit_data_groups_scratch(int64_t nslots);
+hipError_t vit_launch_data_groups(const uint8_t* d_bytes, const vit_packet_rec* d_rec, int64_t nslots, vit_dgroup_rec* d_dg,
+                                  uint32_t max_groups, vit_dgroup_summary* d_sum, uint8_t* d_data, uint32_t data_capacity,
+                                  void* d_scratch, hipStream_t stream);
+void vit_data_groups_host_impl(const uint8_t* bytes, const vit_packet_rec* rec, int64_t nslots, vit_dgroup_rec* dg, uint32_t max_groups,
+                               vit_dgroup_summary* sum, uint8_t* data, uint32_t data_capacity);
 // Multiplex configuration (vit_mci.hip); the caller has checked every argument rule.  One launch; the host form is the
 // same walk on host memory.
 hipError_t vit_launch_mci(const uint8_t* d_fibs, const uint8_t* d_fib_ok, int64_t nfibs, uint32_t G, vit_mci_subch* d_sub,

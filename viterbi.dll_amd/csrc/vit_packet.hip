@@ -44,11 +44,7 @@ unsigned grid_for(long long items, u32 per_block) {
 }
 
 // ---- packets ------------------------------------------------------------------------------------------------------------
-// r * x^(8e) mod g
-constexpr u32 crc_xpow(u32 e, u32 r) {
-    for (u32 k = 0; k < e; k++) r = crc16_step(r, 0);
-    return r;
-}
+// (crc_xpow and crc_mul: vit_crc_dev.h)
 constexpr u32 PKT_X192 = crc_xpow(SLOT, 1u);
 // the register-0 remainder of a whole packet of n slots whose last two bytes are right
 constexpr u32 pkt_good(u32 n) { return crc_xpow(2u, 0xFFFFu ^ crc_xpow(SLOT * n - 2u, 0xFFFFu)); }
@@ -58,16 +54,6 @@ constexpr u32 crc16_of(const char* s, u32 n) {
     return r ^ 0xFFFFu;
 }
 static_assert(crc16_of("123456789", 9) == 0xD64Eu, "CRC-16 0x1021, preset 0xFFFF, complemented");
-
-// r * x mod g for the constant x: the 31-bit carry-less product, its upper half taken through two zero bytes
-template <u32 X>
-__device__ __forceinline__ u32 crc_mul(u32 r) {
-    u32 prod = 0;
-#pragma unroll
-    for (u32 j = 0; j < 16u; j++)
-        if ((X >> j) & 1u) prod ^= r << j;
-    return (prod & 0xFFFFu) ^ crc16_step(crc16_step(prod >> 16, 0), 0);
-}
 
 constexpr u32 PKT_IMG = WAVE * SLOT + 32u;  // 64 slots at any phase, and the seventh dword of the last one
 

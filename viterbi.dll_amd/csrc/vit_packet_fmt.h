@@ -22,6 +22,23 @@ constexpr uint32_t CMD_MASK = 0x80;         // byte 2 bit 7
 constexpr uint32_t USEFUL_MASK = 0x7F;      // byte 2 bits 6..0
 constexpr uint32_t ADDR_PADDING = 0;
 constexpr uint32_t ADDR_FEC = 1022;
+constexpr uint32_t NADDR = 1024;            // the address field's range; 1 ... 1021 and 1023 carry data
+constexpr uint32_t PKT_DATA_OFFSET = 3;     // a packet's useful data follows its three header bytes
+constexpr uint32_t PKT_OVERHEAD = 5;        // header and CRC: useful <= 24 * slots - 5
+constexpr uint32_t MAX_USEFUL = 4 * SLOT - PKT_OVERHEAD;   // 91
+
+// MSC data group (clause 5.3.3), the bytes D[0..L) of a run of packets: byte 0 = extension(1) crc(1) segment(1)
+// user access(1) type(4), byte 1 = continuity(4) repetition(4); then 2 bytes of extension field, 2 bytes of segment
+// field, and the user access field: one byte transport-id flag (bit 4) and length indicator (bits 3..0), then
+// `length indicator` bytes, the first two of them the transport id if the flag is set; the group's CRC is its last 2 bytes
+constexpr uint32_t DG_EXT = 0x80, DG_CRC = 0x40, DG_SEG = 0x20, DG_UA = 0x10, DG_TYPE_MASK = 15;
+constexpr uint32_t DG_FIXED_BYTES = 2, DG_EXT_BYTES = 2, DG_SEG_BYTES = 2, DG_CRC_BYTES = 2;
+constexpr uint32_t DG_UA_TIDF = 0x10, DG_UA_LI_MASK = 15, DG_TID_BYTES = 2;
+constexpr uint32_t DG_HDR_PEEK = 9;         // no field of the header is read at or behind D[9]
+constexpr uint32_t DG_ALIGN = 16;           // a group's bytes start at a multiple of it in d_data
+// vit_dgroup_rec.flags
+constexpr uint32_t DGF_WELLFORMED = 1, DGF_CRCF = 2, DGF_CRC_OK = 4, DGF_SEG = 8, DGF_UA = 16, DGF_TIDF = 32, DGF_EXT = 64;
+constexpr int64_t DG_MAX_SLOTS = 1 << 24;   // of one call: lengths and offsets stay inside 31 bits (91 + 15 bytes a slot)
 
 // FEC frame: application data slots, then FEC packets; FEC packet c starts with {c << 2 | ADDR_FEC >> 8, ADDR_FEC & 255}
 constexpr uint32_t FEC_DATA_SLOTS = 94;
