@@ -580,6 +580,67 @@ int vit_data_groups_dev(const uint8_t *d_bytes, const vit_packet_rec *d_rec, int
 int vit_data_groups_host(const uint8_t *bytes, const vit_packet_rec *rec, int64_t nslots,
                          vit_dgroup_rec *dg, uint32_t max_groups, vit_dgroup_summary *sum,
                          uint8_t *data /* may be NULL */, uint32_t data_capacity);
+/* Packet mode for a whole ensemble: up to 64 streams in one call - for each the FEC phase found on the device, RS(204,188)
+ * in place and the packet records - in a number of launches that does not depend on the table's length, and without the
+ * host waiting between the stages (the per-stream recipe takes the phase from the scores on the host).  The streams lie in
+ * one allocation, typically d_work of vit_ensemble_dev with offset = work_offset[k] of the RSDims 0 entries that FIG 0/2
+ * says are packet mode (the caller's decision).
+ * Layout (vit_packet_table_layout): streams in table order; nslots_k = nframes * framebytes / 24; rec_index is the running
+ * sum of nslots_k; stream k reserves nslots_k / 103 FEC records from fec_index[k] - the count at phase 0, the largest any
+ * phase gives, and for every stream whatever its fec mode - so that d_fec is sized before the device has chosen a
+ * phase.  Only the first nfec of a stream's FEC records are written; the others keep their bytes.
+ * VIT_ERR_ARG, with vit_last_error() naming the entry, for nstreams outside 1 ... 64, a framebytes that is not a multiple
+ * of 24 in 24 ... 1152, nframes 0, fec > 2, phase > 102, a non-zero phase or min_score where the mode does not use it, a
+ * non-zero reserved, two streams whose byte ranges overlap, or more than 2^31 slots in the table. */
+#define VIT_PKT_MAX_STREAMS 64          /* = VIT_ENS_MAX_SUBCH */
+#define VIT_PKT_FEC_NONE   0            /* plain packet mode: no FEC stage, stream untouched */
+#define VIT_PKT_FEC_PHASE  1            /* enhanced packet mode, phase given in the entry */
+#define VIT_PKT_FEC_SEARCH 2            /* enhanced packet mode, phase found on the device */
+#define VIT_PKT_NO_PHASE 0xFFFFFFFFu
+typedef struct vit_pkt_stream {         /* 32 bytes, host table entry */
+    uint64_t offset;                    /* bytes from d_bytes to the stream's first byte; any alignment */
+    uint32_t framebytes;                /* a multiple of 24 in 24 ... 1152 */
+    uint32_t nframes;                   /* logical frames, >= 1 */
+    uint32_t fec;                       /* VIT_PKT_FEC_* */
+    uint32_t phase;                     /* FEC_PHASE: 0 ... 102; otherwise 0 */
+    uint32_t min_score;                 /* FEC_SEARCH: a phase is accepted iff its score >= max(min_score, 1); otherwise 0 */
+    uint32_t reserved;                  /* 0 */
+} vit_pkt_stream;
+typedef struct vit_pkt_layout {
+    uint64_t rec_index[VIT_PKT_MAX_STREAMS];   /* first vit_packet_rec of stream k (slots of earlier streams) */
+    uint64_t fec_index[VIT_PKT_MAX_STREAMS];   /* first vit_fec_rec of stream k */
+    uint64_t nrec, nfecrec;                    /* sizes of d_rec, d_fec in records */
+    uint64_t bytes_end;                        /* max(offset + 24*nslots): what d_bytes must hold */
+} vit_pkt_layout;
+typedef struct vit_pkt_stream_rec {     /* 16 bytes per stream, written completely */
+    uint32_t phase;                     /* the phase used, or VIT_PKT_NO_PHASE (FEC_NONE, or no score reached min_score) */
+    uint32_t score, runner_up;          /* FEC_SEARCH: largest score and the largest score at any OTHER phase; otherwise 0 */
+    uint32_t nfec;                      /* FEC frames decoded = vit_packet_fec_count(nslots, phase), 0 without a phase */
+} vit_pkt_stream_rec;
+/* Host only, needs no GPU. */
+int vit_packet_table_layout(const vit_pkt_stream *h_tab, uint32_t nstreams, vit_pkt_layout *h_out);
+/* For stream k, with s = d_bytes + offset and nslots = nslots_k, byte for byte what the per-stream calls write:
+ *   FEC_SEARCH   the scores are those of vit_packet_fec_sync_dev(s, nslots, .); score is the largest of the 103, phase
+ *                the SMALLEST p that has it, runner_up the largest score at any other p.  If score < max(min_score, 1)
+ *                the stream has no phase: VIT_PKT_NO_PHASE, nfec 0, no byte of the stream changed.
+ *   with a phase (given or found): the stream and the records are those of vit_packet_fec_dev(s, s, nslots, phase,
+ *                d_fec + fec_index[k]) - always in place; a workgroup of clean rows writes no byte of the stream.
+ *   then, for every stream, the records of vit_packets_dev(s, framebytes, nframes, d_rec + rec_index[k]) on the corrected
+ *                bytes: stream k's block of d_rec, together with s, is what vit_data_groups_dev takes.
+ * d_score, if not NULL: words 103k ... 103k+102 hold stream k's scores, 0 for streams of the other two modes; if NULL the
+ * scores live in the calling thread's scratch.  d_srec[k] is written for every stream.  Bytes of d_bytes outside the
+ * streams, FEC records beyond nfec and anything outside the named ranges are neither read nor written; the result does
+ * not depend on scheduling.  The table is validated as by vit_packet_table_layout; then d_bytes, d_srec and d_rec must
+ * not be NULL, d_srec, d_fec, d_rec and d_score must be 4-byte aligned, and d_fec may be NULL only when nfecrec is 0.
+ * Everything is enqueued on `stream`: no host synchronisation and no device-to-host copy.
+ * Launches, whatever nstreams: a clear of the scores; the sync, a workgroup per FEC_SEARCH stream and 1024 slots; the
+ * pick, a wavefront per stream, which writes d_srec; the FEC, a workgroup per 20 frames of one stream, sized from the
+ * bound nslots / 103 (the given phase's count for FEC_PHASE) - a workgroup whose first frame is not below nfec leaves at
+ * once; the packets, a wavefront's round on 64 / (framebytes/24) logical frames of one stream.  A stage that no entry
+ * uses is skipped (clear and sync without a FEC_SEARCH entry and without d_score; the FEC without a frame to decode). */
+int vit_packet_table_dev(uint8_t *d_bytes, const vit_pkt_stream *h_tab, uint32_t nstreams,
+                         vit_pkt_stream_rec *d_srec, vit_fec_rec *d_fec, vit_packet_rec *d_rec,
+                         uint32_t *d_score /* uint32[103*nstreams], may be NULL */, void *stream);
 
 /* Multiplex configuration: from the FIBs that vit_decode_fic_dev leaves on the device to the sub-channel table that
  * vit_ensemble_dev takes - FIG 0/0 (ensemble identifier, CIF counter), FIG 0/1 (sub-channel organisation) and FIG 0/2

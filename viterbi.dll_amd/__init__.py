@@ -38,7 +38,7 @@ EXPORTS = [
     "vit_ofdm_tii_dev", "vit_tii_pair_bins", "vit_tii_main_id",
     "vit_resample_taps", "vit_resample_out_count", "vit_iq_resample_dev",
     "vit_packet_fec_sync_dev", "vit_packet_fec_count", "vit_packet_fec_dev", "vit_packet_fec_frame_host", "vit_packets_dev",
-    "vit_data_groups_dev", "vit_data_groups_host",
+    "vit_data_groups_dev", "vit_data_groups_host", "vit_packet_table_layout", "vit_packet_table_dev",
     "vit_mci_fibs_dev", "vit_mci_fibs_host", "vit_eep_profile", "vit_mci_ens_table",
     "vit_decode_stream_multi",
 ]
@@ -69,6 +69,15 @@ PACKET_REC_DTYPE = np.dtype([("kind", "u1"), ("crc_ok", "u1"), ("nslots", "u1"),
 PKT_CONT, PKT_DATA, PKT_PADDING, PKT_FEC, PKT_OVERRUN = 0, 1, 2, 3, 4
 PKT_SLOT, FEC_FRAME_SLOTS, FEC_FRAME_BYTES = 24, 103, 2472
 PKT_LAST, PKT_FIRST = 4, 8  # vit_packet_rec.flags
+# packet mode over a table of streams: vit_pkt_stream per entry, vit_pkt_layout, vit_pkt_stream_rec per stream
+PKT_MAX_STREAMS = 64
+PKT_FEC_NONE, PKT_FEC_PHASE, PKT_FEC_SEARCH = 0, 1, 2
+PKT_NO_PHASE = 0xFFFFFFFF
+PKT_STREAM_DTYPE = np.dtype([("offset", "<u8"), ("framebytes", "<u4"), ("nframes", "<u4"), ("fec", "<u4"), ("phase", "<u4"),
+                             ("min_score", "<u4"), ("reserved", "<u4")])
+PKT_LAYOUT_DTYPE = np.dtype([("rec_index", "<u8", (PKT_MAX_STREAMS,)), ("fec_index", "<u8", (PKT_MAX_STREAMS,)), ("nrec", "<u8"),
+                             ("nfecrec", "<u8"), ("bytes_end", "<u8")])
+PKT_STREAM_REC_DTYPE = np.dtype([("phase", "<u4"), ("score", "<u4"), ("runner_up", "<u4"), ("nfec", "<u4")])
 # MSC data groups: vit_dgroup_rec per group, vit_dgroup_summary per call
 DGROUP_REC_DTYPE = np.dtype([("first_slot", "<u4"), ("last_slot", "<u4"), ("npackets", "<u4"), ("offset", "<u4"), ("length", "<u4"),
                              ("address", "<u2"), ("segment", "<u2"), ("transport_id", "<u2"), ("payload_offset", "<u2"),
@@ -287,6 +296,8 @@ def lib():
         L.vit_packet_fec_dev.argtypes = [vp, vp, C.c_int64, C.c_uint32, vp, vp]
         L.vit_packet_fec_frame_host.argtypes = [vp, vp]
         L.vit_packets_dev.argtypes = [vp, C.c_uint32, C.c_int64, vp, vp]
+        L.vit_packet_table_layout.argtypes = [vp, C.c_uint32, vp]
+        L.vit_packet_table_dev.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, vp]
         L.vit_data_groups_dev.argtypes = [vp, vp, C.c_int64, vp, C.c_uint32, vp, vp, C.c_uint32, vp]
         L.vit_data_groups_host.argtypes = [vp, vp, C.c_int64, vp, C.c_uint32, vp, vp, C.c_uint32]
         L.vit_mci_fibs_dev.argtypes = [vp, vp, C.c_int64, C.c_uint32, vp, vp, vp, vp]
@@ -626,6 +637,30 @@ def packets_dev(d_bytes, framebytes, nframes, d_rec, stream=None):
     """one PACKET_REC_DTYPE record (8 bytes, in the uint8 tensor d_rec) per 24-byte slot of nframes logical frames of
     framebytes bytes"""
     _check(lib().vit_packets_dev(_ptr(d_bytes), framebytes, nframes, _ptr(d_rec), _stream_ptr(stream)), "vit_packets_dev")
+
+
+def _pkt_table(tab):
+    """a stream table (PKT_STREAM_DTYPE array, or anything np.asarray turns into one) -> contiguous array"""
+    return np.ascontiguousarray(np.asarray(tab, PKT_STREAM_DTYPE).reshape(-1))
+
+
+def packet_table_layout(tab):
+    """host, no GPU: the layout of a stream table (PKT_STREAM_DTYPE) -> one PKT_LAYOUT_DTYPE record (rec_index, fec_index per
+    entry; nrec, nfecrec, bytes_end); ViterbiError for a table that breaks a rule of include/viterbi_amd.h"""
+    tab = _pkt_table(tab)
+    out = np.zeros(1, PKT_LAYOUT_DTYPE)
+    _check(lib().vit_packet_table_layout(_np(tab), tab.size, _np(out)), "vit_packet_table_layout")
+    return out[0]
+
+
+def packet_table_dev(d_bytes, tab, d_srec, d_fec, d_rec, d_score=None, stream=None):
+    """packet mode over every stream of the table (PKT_STREAM_DTYPE) in a fixed number of launches: FEC phase found on the
+    device, RS(204,188) in place in d_bytes, packet records.  uint8 CUDA tensors in the layout of packet_table_layout:
+    d_srec one PKT_STREAM_REC_DTYPE record (16 bytes) per stream, d_fec FEC_REC_DTYPE records (None if nfecrec is 0), d_rec
+    PACKET_REC_DTYPE records; d_score (optional) 103 uint32 per stream"""
+    tab = _pkt_table(tab)
+    _check(lib().vit_packet_table_dev(_ptr(d_bytes), _np(tab), tab.size, _ptr(d_srec), _ptr(d_fec), _ptr(d_rec), _ptr(d_score),
+                                      _stream_ptr(stream)), "vit_packet_table_dev")
 
 
 def data_groups_dev(d_bytes, d_rec, nslots, d_dg, max_groups, d_sum, d_data=None, data_capacity=0, stream=None):

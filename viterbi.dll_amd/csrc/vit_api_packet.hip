@@ -1,5 +1,8 @@
 // vit_api_packet.hip -- the C ABI of packet mode (include/viterbi_amd.h, "Packet mode"): argument rules and launches
 // only; the kernels and the host twin are in vit_packet.hip, the format's constants in vit_packet_fmt.h.
+#include <algorithm>
+#include <utility>
+
 #include "vit_host.h"
 #include "vit_packet_fmt.h"
 
@@ -62,6 +65,119 @@ int vit_packets_dev(const uint8_t* d_bytes, uint32_t framebytes, int64_t nframes
                        "aligned)", framebytes, (long long)nframes);
     LAUNCHCHK("packet launch failed: %s", vit_launch_packets(d_bytes, framebytes, nframes, d_rec, (hipStream_t)stream));
     return VIT_OK;
+}
+
+namespace {
+
+// The table's rules, its layout (h_out optional) and the table as the kernels read it (tab optional); false, with the
+// error text naming the entry, if a rule is broken.
+bool pkt_table(const char* who, const vit_pkt_stream* h_tab, uint32_t nstreams, vit_pkt_layout* h_out, VitPktTable* tab) {
+    if (!h_tab || nstreams < 1u || nstreams > VIT_PKT_MAX_STREAMS) {
+        set_err("%s: bad arguments (nstreams=%u, 1 ... %u; h_tab)", who, nstreams, (unsigned)VIT_PKT_MAX_STREAMS);
+        return false;
+    }
+    vit_pkt_layout lay = {};
+    VitPktTable t = {};
+    uint64_t npkt = 0, nsync = 0, nfecwg = 0;
+    std::pair<uint64_t, uint32_t> order[VIT_PKT_MAX_STREAMS];  // (offset, entry)
+    for (uint32_t k = 0; k < nstreams; k++) {
+        const vit_pkt_stream& s = h_tab[k];
+        const char* why = nullptr;
+        if (s.framebytes == 0 || s.framebytes > MAX_FRAMEBYTES || s.framebytes % SLOT) why = "framebytes must be a multiple of 24 in 24 ... 1152";
+        else if (s.nframes == 0) why = "nframes must be at least 1";
+        else if (s.fec > VIT_PKT_FEC_SEARCH) why = "fec must be 0 (none), 1 (phase given) or 2 (phase searched)";
+        else if (s.phase >= FEC_SLOTS) why = "phase must be 0 ... 102";
+        else if (s.phase && s.fec != VIT_PKT_FEC_PHASE) why = "phase must be 0 unless fec is 1 (phase given)";
+        else if (s.min_score && s.fec != VIT_PKT_FEC_SEARCH) why = "min_score must be 0 unless fec is 2 (phase searched)";
+        else if (s.reserved) why = "reserved must be 0";
+        const uint64_t S = s.framebytes / SLOT, nslots = why ? 0 : (uint64_t)s.nframes * S;
+        if (!why && lay.nrec + nslots > 0x80000000ull) why = "the table holds more than 2^31 slots";
+        else if (!why && s.offset + SLOT * nslots < s.offset) why = "offset + 24*nslots must fit 64 bits";
+        if (why) {
+            set_err("%s: bad arguments (entry %u: %s; offset=%llu framebytes=%u nframes=%u fec=%u phase=%u min_score=%u reserved=%u)", who,
+                    k, why, (unsigned long long)s.offset, s.framebytes, s.nframes, s.fec, s.phase, s.min_score, s.reserved);
+            return false;
+        }
+        lay.rec_index[k] = lay.nrec;
+        lay.fec_index[k] = lay.nfecrec;
+        VitPktEntry& e = t.e[k];
+        e.offset = s.offset;
+        e.nframes = s.nframes;
+        e.nslots = (uint32_t)nslots;
+        e.rec0 = (uint32_t)lay.nrec;
+        e.fec0 = (uint32_t)lay.nfecrec;
+        e.pkt0 = (uint32_t)npkt;
+        e.sync0 = (uint32_t)nsync;
+        e.fecwg0 = (uint32_t)nfecwg;
+        e.S = (uint8_t)S;
+        e.fec = (uint8_t)s.fec;
+        e.phase = (uint8_t)s.phase;
+        lay.nrec += nslots;
+        lay.nfecrec += nslots / FEC_SLOTS;
+        lay.bytes_end = std::max(lay.bytes_end, s.offset + SLOT * nslots);
+        const uint64_t G = 64u / S;
+        npkt += (s.nframes + G - 1u) / G;
+        if (s.fec == VIT_PKT_FEC_SEARCH) nsync += (nslots + VIT_PKT_SYNC_CHUNK - 1u) / VIT_PKT_SYNC_CHUNK;
+        // frames the stream can hold at most: at the given phase, or at phase 0 where the device chooses
+        const uint64_t bound = s.fec == VIT_PKT_FEC_NONE ? 0u : (uint64_t)fec_count((int64_t)nslots, s.phase);
+        nfecwg += (bound + 19u) / 20u;
+        order[k] = {s.offset, k};
+    }
+    // (passes and workgroups are fewer than slots: they fit 32 bits with them)
+    std::sort(order, order + nstreams);
+    for (uint32_t j = 1; j < nstreams; j++) {
+        const uint32_t a = order[j - 1u].second, b = order[j].second;
+        if (h_tab[a].offset + (uint64_t)SLOT * t.e[a].nslots > h_tab[b].offset) {
+            set_err("%s: bad arguments (entries %u and %u overlap: offset=%llu, %llu bytes; offset=%llu)", who, a, b,
+                    (unsigned long long)h_tab[a].offset, (unsigned long long)SLOT * t.e[a].nslots, (unsigned long long)h_tab[b].offset);
+            return false;
+        }
+    }
+    t.nstreams = nstreams;
+    t.npkt = (uint32_t)npkt;
+    t.nsync = (uint32_t)nsync;
+    t.nfecwg = (uint32_t)nfecwg;
+    if (h_out) *h_out = lay;
+    if (tab) *tab = t;
+    return true;
+}
+
+}  // namespace
+
+int vit_packet_table_layout(const vit_pkt_stream* h_tab, uint32_t nstreams, vit_pkt_layout* h_out) {
+    if (!h_out) return bad_arg("vit_packet_table_layout: bad arguments (h_out)");
+    return pkt_table("vit_packet_table_layout", h_tab, nstreams, h_out, nullptr) ? VIT_OK : VIT_ERR_ARG;
+}
+
+int vit_packet_table_dev(uint8_t* d_bytes, const vit_pkt_stream* h_tab, uint32_t nstreams, vit_pkt_stream_rec* d_srec, vit_fec_rec* d_fec,
+                         vit_packet_rec* d_rec, uint32_t* d_score, void* stream) {
+    static const char* const who = "vit_packet_table_dev";
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    vit_pkt_layout lay;
+    VitPktTable tab;
+    if (!pkt_table(who, h_tab, nstreams, &lay, &tab)) return VIT_ERR_ARG;
+    const char* why = nullptr;
+    if (!d_bytes || !d_srec || !d_rec) why = "NULL d_bytes, d_srec or d_rec";
+    else if (misaligned4(d_srec) || misaligned4(d_fec) || misaligned4(d_rec) || misaligned4(d_score)) why = "d_srec, d_fec, d_rec and d_score must be 4-byte aligned";
+    else if (!d_fec && lay.nfecrec > 0) why = "d_fec may be NULL only when the layout's nfecrec is 0";
+    if (why) return bad_arg("%s: bad arguments (%s)", who, why);
+    const hipStream_t s = (hipStream_t)stream;
+    uint32_t min_score[VIT_PKT_MAX_STREAMS];
+    for (uint32_t k = 0; k < nstreams; k++) min_score[k] = h_tab[k].min_score;
+    // Nothing below waits for the device or copies from it: a memset and four kernels on `stream`, and around them the
+    // scratch lease's event (a wait and a record on the stream) when the scores live in the thread's scratch.
+    const bool search = tab.nsync > 0, own_scores = search && !d_score;
+    ScratchLease scratch;
+    if (own_scores) {
+        const int rc = scratch.begin((size_t)nstreams * FEC_SLOTS * sizeof(uint32_t), 0, s);
+        if (rc != VIT_OK) return rc;
+        d_score = scratch.sym<uint32_t>();
+    }
+    if (d_score) LAUNCHCHK("packet table sync launch failed: %s", vit_launch_pkt_table_sync(d_bytes, tab, d_score, s));
+    LAUNCHCHK("packet table pick launch failed: %s", vit_launch_pkt_table_pick(tab, d_score, min_score, d_srec, s));
+    LAUNCHCHK("packet table FEC launch failed: %s", vit_launch_pkt_table_fec(d_bytes, tab, d_srec, d_fec, s));
+    LAUNCHCHK("packet table packets launch failed: %s", vit_launch_pkt_table_packets(d_bytes, tab, d_rec, s));
+    return own_scores ? scratch.end() : VIT_OK;
 }
 
 namespace {

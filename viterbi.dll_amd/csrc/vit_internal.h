@@ -163,6 +163,41 @@ hipError_t vit_launch_fec(const uint8_t* d_stream, uint8_t* d_out, int64_t nslot
 void vit_fec_frame_host(uint8_t* frame, vit_fec_rec* h_out);
 hipError_t vit_launch_packets(const uint8_t* d_bytes, uint32_t framebytes, int64_t nframes, vit_packet_rec* d_rec,
                               hipStream_t stream);
+// Packet mode for a table of streams (vit_packet_table.hip; include/viterbi_amd.h, vit_pkt_stream): the table as the
+// kernels read it, BY VALUE in the kernel arguments.  Entry k holds where stream k's bytes and records start and where
+// its share of each stage's passes starts; a pass finds its stream with vit_table_find - an entry without passes in a
+// stage (a stream that is not FEC_SEARCH among the sync workgroups) is never the answer.  The ranges end at the totals.
+struct VitPktEntry {
+    uint64_t offset;    // bytes from d_bytes
+    uint32_t nframes;   // logical frames
+    uint32_t nslots;    // nframes * S
+    uint32_t rec0;      // first vit_packet_rec (slots of earlier streams)
+    uint32_t fec0;      // first vit_fec_rec
+    uint32_t pkt0;      // first packet pass: a wavefront's round of 64 / S logical frames of ONE stream
+    uint32_t sync0;     // first sync workgroup: one per VIT_PKT_SYNC_CHUNK slots of a FEC_SEARCH stream
+    uint32_t fecwg0;    // first FEC workgroup: one per 20 FEC frames the stream can hold at most (at its given phase)
+    uint8_t S;          // slots per logical frame, 1 ... 48
+    uint8_t fec;        // VIT_PKT_FEC_*
+    uint8_t phase;      // FEC_PHASE: the host's phase
+    uint8_t pad;
+};
+#define VIT_PKT_SYNC_CHUNK 1024u  // slots: four per thread, as the uniform launch's grid
+struct VitPktTable {
+    uint32_t nstreams, npkt, nsync, nfecwg;  // the totals
+    VitPktEntry e[VIT_PKT_MAX_STREAMS];
+};
+static_assert(sizeof(VitPktEntry) == 40 && sizeof(VitPktTable) == 16 + 40 * VIT_PKT_MAX_STREAMS && sizeof(VitPktTable) + 64 <= 4096,
+              "2576 bytes: the table and five pointers fit the 4 KB of kernel arguments");
+// The launches of vit_packet_table_dev, in order; the caller has checked every argument rule.  d_score: 103 words per
+// stream, cleared on the stream in front of the sync kernel (vit_launch_pkt_table_sync does both; it is called only when
+// the scores are wanted - a FEC_SEARCH entry, or the caller's d_score); the pick reads them only for FEC_SEARCH entries
+// and writes every stream's vit_pkt_stream_rec; the FEC workgroups read phase and nfec from d_srec.
+hipError_t vit_launch_pkt_table_sync(const uint8_t* d_bytes, const VitPktTable& tab, uint32_t* d_score, hipStream_t stream);
+hipError_t vit_launch_pkt_table_pick(const VitPktTable& tab, const uint32_t* d_score, const uint32_t* h_min_score,
+                                     vit_pkt_stream_rec* d_srec, hipStream_t stream);
+hipError_t vit_launch_pkt_table_fec(uint8_t* d_bytes, const VitPktTable& tab, const vit_pkt_stream_rec* d_srec, vit_fec_rec* d_fec,
+                                    hipStream_t stream);
+hipError_t vit_launch_pkt_table_packets(const uint8_t* d_bytes, const VitPktTable& tab, vit_packet_rec* d_rec, hipStream_t stream);
 // Data groups (vit_dgroup.hip); the caller has checked every argument rule.  d_scratch: vit_data_groups_scratch(nslots)
 // bytes, 16-byte aligned; its first 256 bytes are cleared on the stream in front of the kernels.  The host form is the
 // same definition as a walk per address.
@@ -199,16 +234,23 @@ struct VitEnsTable {
     uint32_t max_rsdims, pad[3];
     VitEnsEntry e[VIT_ENS_MAX_SUBCH];
 };
-// vit_ens_find<&VitEnsEntry::frame0>(tab, x): the sub-channel whose frames hold frame x < tab.nframes (rec0, pass0 alike)
-template <uint32_t VitEnsEntry::*START>
-__host__ __device__ inline uint32_t vit_ens_find(const VitEnsTable& tab, uint32_t x) {
-    uint32_t lo = 0, hi = tab.nsub;  // e[0]'s start is 0
+// The lookup of every table that travels in the kernel arguments (VitEnsTable here, VitPktTable below):
+// vit_table_find<Entry, &Entry::start>(e, n, x) is the largest k < n with e[k].start <= x, for starts that do not
+// decrease and begin with e[0].start == 0.
+template <class Entry, uint32_t Entry::*START>
+__host__ __device__ inline uint32_t vit_table_find(const Entry* e, uint32_t n, uint32_t x) {
+    uint32_t lo = 0, hi = n;  // e[0]'s start is 0
     while (hi - lo > 1u) {
         const uint32_t mid = (lo + hi) >> 1;
-        if (tab.e[mid].*START <= x) lo = mid;
+        if (e[mid].*START <= x) lo = mid;
         else hi = mid;
     }
     return lo;
+}
+// vit_ens_find<&VitEnsEntry::frame0>(tab, x): the sub-channel whose frames hold frame x < tab.nframes (rec0, pass0 alike)
+template <uint32_t VitEnsEntry::*START>
+__host__ __device__ inline uint32_t vit_ens_find(const VitEnsTable& tab, uint32_t x) {
+    return vit_table_find<VitEnsEntry, START>(tab.e, tab.nsub, x);
 }
 // what only the descriptor kernel needs of a sub-channel
 struct VitEnsSource {
