@@ -90,6 +90,14 @@ DGROUP_MAX_SLOTS = 1 << 24
 # there): the link pass's tile and the chunk of one workgroup, the block of the prefix sum, the slots a gathering wavefront
 # takes per step.  Every group is gathered by one wavefront: there is no wavefront/workgroup threshold.
 DGROUP_GEOMETRY = {"link_tile": 1024, "link_chunk": 16384, "number_block": 4096, "gather_step": 64}
+# the sizes at which the kernels of csrc/vit_ofdm_acq.hip change their partition (TILE_CHUNKS and the chunk's 16 bytes,
+# SEARCH_TILE, WINDOW_MAX there): the 16-byte chunks a wavefront of the power kernel takes per trip, the candidates the
+# search holds in LDS at once, the longest window the LDS is sized for
+ACQ_GEOMETRY = {"chunk_bytes": 16, "tile_chunks": 256, "search_tile": 2048, "window_max": 4096}
+# and of csrc/vit_ofdm_tii.hip (GROUP_TPB, SLOTS_MAX there, and the argument rules' caps): the threads of the group kernel,
+# whose three loops step by that many slots or combs, the slots its LDS holds, and the most groups, frames per estimate
+# and repetitions the call takes
+TII_GEOMETRY = {"group_threads": 256, "slots_max": 1024, "groups_max": 32, "navg_max": 256, "nrep_max": 8}
 
 # multiplex configuration (include/viterbi_amd.h): vit_mci_subch per (group, SubChId), vit_mci_group per group
 MCI_SUBCH_DTYPE = np.dtype([("org", "<u4"), ("comp", "<u4"), ("sid", "<u4"), ("n_org", "<u2"), ("n_org_other", "<u2"),

@@ -28,14 +28,16 @@ namespace {
 typedef uint32_t u32;
 typedef uint64_t u64;
 
+// (the chunk's 16 bytes, TILE_CHUNKS, SEARCH_TILE and WINDOW_MAX stand again in viterbi.dll_amd/__init__.py, ACQ_GEOMETRY: the
+// tests take their edges from it)
 constexpr u32 ROWS = 4u;             // 16-byte chunks a lane has in flight
-constexpr u32 TILE_CHUNKS = 64u * ROWS;
+constexpr u32 TILE_CHUNKS = 64u * ROWS;  // ACQ_GEOMETRY["tile_chunks"]
 constexpr u32 POWER_TPB = 256u;
 constexpr u32 POWER_MAX_GRID = 8192u;  // the waves stride over the tiles beyond it
 
 constexpr u32 SEARCH_TPB = 256u;
-constexpr u32 SEARCH_TILE = 2048u;   // candidates per LDS tile
-constexpr u32 WINDOW_MAX = 4096u;    // Ln, Lr at most
+constexpr u32 SEARCH_TILE = 2048u;   // candidates per LDS tile: ACQ_GEOMETRY["search_tile"]
+constexpr u32 WINDOW_MAX = 4096u;    // Ln, Lr at most: ACQ_GEOMETRY["window_max"]
 constexpr u32 SEARCH_LDS = SEARCH_TILE + 2u * WINDOW_MAX;  // floats: 40 KiB
 constexpr u32 SEARCH_MAX_GRID = 1u << 20;
 constexpr u32 NONE = 0xFFFFFFFFu;    // no candidate

@@ -29,8 +29,10 @@ namespace {
 
 using namespace vit_fft;
 
-constexpr u32 GROUP_TPB = 256u;    // navg <= 256: one thread per frame of a group
-constexpr u32 SLOTS_MAX = 1024u;   // Gp * C at most
+// (both stand again in viterbi.dll_amd/__init__.py, TII_GEOMETRY, with the caps of the argument rules - Gp <= 32, navg <= 256,
+// R <= 8: the tests take their edges from it)
+constexpr u32 GROUP_TPB = 256u;    // navg <= 256: one thread per frame of a group; TII_GEOMETRY["group_threads"]
+constexpr u32 SLOTS_MAX = 1024u;   // Gp * C at most: TII_GEOMETRY["slots_max"]
 
 struct TiiArgs {
     const float2* iq;
