@@ -641,6 +641,57 @@ int vit_packet_table_layout(const vit_pkt_stream *h_tab, uint32_t nstreams, vit_
 int vit_packet_table_dev(uint8_t *d_bytes, const vit_pkt_stream *h_tab, uint32_t nstreams,
                          vit_pkt_stream_rec *d_srec, vit_fec_rec *d_fec, vit_packet_rec *d_rec,
                          uint32_t *d_score /* uint32[103*nstreams], may be NULL */, void *stream);
+/* Data groups for a whole ensemble: vit_data_groups_dev over up to 64 streams in one call, in a number of launches that
+ * does not depend on the table's length - the stage behind vit_packet_table_dev, whose d_rec it takes as it stands
+ * (rec_index = vit_pkt_layout.rec_index[k], offset = the packet table's offset).
+ * Layout (vit_data_groups_table_layout): streams in table order; dg_index is the running sum of max_groups, data_offset
+ * the running sum of data_capacity rounded up to a multiple of 16 (a records-only stream takes no room); ndg and
+ * data_bytes are the sums' ends, bytes_end = max(offset + 24*nslots) and rec_end = max(rec_index + nslots).
+ * Definition: stream k's records d_dg + dg_index[k], its summary d_sum[k] and its bytes d_data + data_offset[k] hold, byte
+ * for byte, what
+ *   vit_data_groups_dev(d_bytes + offset, d_rec + rec_index, nslots, d_dg + dg_index[k], max_groups, &d_sum[k],
+ *                       records_only ? NULL : d_data + data_offset[k], data_capacity, stream)
+ * writes there, and nothing else is written.  Every rule of that call holds per stream: first_slot, last_slot and
+ * open_from count from the stream's own slot 0, a packet is usable only if it ends inside the stream's own nslots, groups
+ * are numbered and placed per stream (offsets from the stream's block of d_data, multiples of 16), only the stream's
+ * first nwritten records and the written groups' bytes are written, a stream with max_groups 0 still gets its summary, no
+ * byte outside the streams' named ranges is read, and the result does not depend on scheduling.  The input is only read:
+ * streams and record blocks may overlap or repeat; the layout keeps the outputs apart.  A NULL d_data makes every stream
+ * records-only (it is allowed only where no stream asks for room).
+ * Errors: VIT_ERR_NO_DEVICE first.  VIT_ERR_ARG, with vit_last_error() naming the entry, for nstreams outside 1 ... 64, an
+ * nslots outside 1 ... 1<<24, records_only > 1, records_only 1 with a non-zero data_capacity, an offset + 24*nslots or
+ * rec_index + nslots that does not fit 64 bits, more than 1<<26 slots in the table (the call keeps 16 bytes of scratch per
+ * slot: 1 GiB there), or a dg_index or data_offset that would pass 2^32.  For the call also a NULL d_bytes, d_rec or
+ * d_sum, a NULL d_dg with ndg > 0, a NULL d_data when some entry has records_only 0 and data_capacity > 0, or a d_rec,
+ * d_dg or d_sum that is not 4-byte aligned.
+ * Launches, whatever nstreams, all on `stream`, with no host synchronisation and no device-to-host copy: one clear of the
+ * streams' scratch headers, then the kernels of vit_data_groups_dev with each workgroup's stream found from the table in
+ * the kernel arguments - presence (a workgroup per 4096 slots of a stream); link totals (per address and chunk of 16384
+ * slots but a stream's last; only if some stream has more than one chunk); link emit (per address and chunk); sums (a
+ * workgroup per 4096 slots); bases (a workgroup per stream); place (as sums); gather (a wavefront per group that may be
+ * written, max(1, min(max_groups, nslots)) per stream, at most 4096 of them; they number the groups that are written
+ * through the table from the streams' counts and stride over them; wavefront k also writes stream k's summary).  Scratch
+ * (the calling thread's): 256 bytes per stream and what vit_data_groups_dev takes for each. */
+#define VIT_DG_MAX_STREAMS 64               /* = VIT_PKT_MAX_STREAMS */
+typedef struct vit_dg_stream {              /* 32 bytes, host table entry */
+    uint64_t offset;                        /* bytes from d_bytes to the stream's first byte; any alignment */
+    uint64_t rec_index;                     /* the stream's first vit_packet_rec in d_rec */
+    uint32_t nslots;                        /* 1 ... 1<<24 */
+    uint32_t max_groups;                    /* as in vit_data_groups_dev; may be 0 */
+    uint32_t data_capacity;                 /* as in vit_data_groups_dev */
+    uint32_t records_only;                  /* 0, or 1 = this stream as with d_data NULL; then data_capacity must be 0 */
+} vit_dg_stream;
+typedef struct vit_dg_layout {
+    uint64_t dg_index[VIT_DG_MAX_STREAMS];     /* first vit_dgroup_rec of stream k: running sum of max_groups */
+    uint64_t data_offset[VIT_DG_MAX_STREAMS];  /* stream k's block of d_data: running sum of data_capacity rounded up to 16 */
+    uint64_t ndg, data_bytes;                  /* sizes of d_dg (records) and d_data (bytes) */
+    uint64_t bytes_end, rec_end;               /* what d_bytes (bytes) and d_rec (records) must hold */
+} vit_dg_layout;
+/* Host only, needs no GPU. */
+int vit_data_groups_table_layout(const vit_dg_stream *h_tab, uint32_t nstreams, vit_dg_layout *h_out);
+int vit_data_groups_table_dev(const uint8_t *d_bytes, const vit_packet_rec *d_rec, const vit_dg_stream *h_tab,
+                              uint32_t nstreams, vit_dgroup_rec *d_dg, vit_dgroup_summary *d_sum /* [nstreams] */,
+                              uint8_t *d_data /* may be NULL */, void *stream);
 
 /* Multiplex configuration: from the FIBs that vit_decode_fic_dev leaves on the device to the sub-channel table that
  * vit_ensemble_dev takes - FIG 0/0 (ensemble identifier, CIF counter), FIG 0/1 (sub-channel organisation) and FIG 0/2

@@ -39,6 +39,7 @@ EXPORTS = [
     "vit_resample_taps", "vit_resample_out_count", "vit_iq_resample_dev",
     "vit_packet_fec_sync_dev", "vit_packet_fec_count", "vit_packet_fec_dev", "vit_packet_fec_frame_host", "vit_packets_dev",
     "vit_data_groups_dev", "vit_data_groups_host", "vit_packet_table_layout", "vit_packet_table_dev",
+    "vit_data_groups_table_layout", "vit_data_groups_table_dev",
     "vit_mci_fibs_dev", "vit_mci_fibs_host", "vit_eep_profile", "vit_mci_ens_table",
     "vit_decode_stream_multi",
 ]
@@ -90,6 +91,12 @@ DGROUP_MAX_SLOTS = 1 << 24
 # there): the link pass's tile and the chunk of one workgroup, the block of the prefix sum, the slots a gathering wavefront
 # takes per step.  Every group is gathered by one wavefront: there is no wavefront/workgroup threshold.
 DGROUP_GEOMETRY = {"link_tile": 1024, "link_chunk": 16384, "number_block": 4096, "gather_step": 64}
+# data groups over a table of streams: vit_dg_stream per entry, vit_dg_layout
+DG_MAX_STREAMS = 64
+DG_STREAM_DTYPE = np.dtype([("offset", "<u8"), ("rec_index", "<u8"), ("nslots", "<u4"), ("max_groups", "<u4"), ("data_capacity", "<u4"),
+                            ("records_only", "<u4")])
+DG_LAYOUT_DTYPE = np.dtype([("dg_index", "<u8", (DG_MAX_STREAMS,)), ("data_offset", "<u8", (DG_MAX_STREAMS,)), ("ndg", "<u8"),
+                            ("data_bytes", "<u8"), ("bytes_end", "<u8"), ("rec_end", "<u8")])
 # the sizes at which the kernels of csrc/vit_ofdm_acq.hip change their partition (TILE_CHUNKS and the chunk's 16 bytes,
 # SEARCH_TILE, WINDOW_MAX there): the 16-byte chunks a wavefront of the power kernel takes per trip, the candidates the
 # search holds in LDS at once, the longest window the LDS is sized for
@@ -306,6 +313,8 @@ def lib():
         L.vit_packets_dev.argtypes = [vp, C.c_uint32, C.c_int64, vp, vp]
         L.vit_packet_table_layout.argtypes = [vp, C.c_uint32, vp]
         L.vit_packet_table_dev.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, vp]
+        L.vit_data_groups_table_layout.argtypes = [vp, C.c_uint32, vp]
+        L.vit_data_groups_table_dev.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, vp, vp]
         L.vit_data_groups_dev.argtypes = [vp, vp, C.c_int64, vp, C.c_uint32, vp, vp, C.c_uint32, vp]
         L.vit_data_groups_host.argtypes = [vp, vp, C.c_int64, vp, C.c_uint32, vp, vp, C.c_uint32]
         L.vit_mci_fibs_dev.argtypes = [vp, vp, C.c_int64, C.c_uint32, vp, vp, vp, vp]
@@ -692,6 +701,30 @@ def data_groups_host(stream, rec, max_groups, data_capacity):
     _check(lib().vit_data_groups_host(_np(stream), _np(rec), rec.size, _np(dg), max_groups, _np(summary),
                                       None if data is None else _np(data), data_capacity or 0), "vit_data_groups_host")
     return dg[:int(summary["nwritten"][0])], summary[0], None if data is None else data[:data_capacity]
+
+
+def _dg_table(tab):
+    """a data group table (DG_STREAM_DTYPE array, or anything np.asarray turns into one) -> contiguous array"""
+    return np.ascontiguousarray(np.asarray(tab, DG_STREAM_DTYPE).reshape(-1))
+
+
+def data_groups_table_layout(tab):
+    """host, no GPU: the layout of a data group table (DG_STREAM_DTYPE) -> one DG_LAYOUT_DTYPE record (dg_index, data_offset
+    per entry; ndg, data_bytes, bytes_end, rec_end); ViterbiError for a table that breaks a rule of include/viterbi_amd.h"""
+    tab = _dg_table(tab)
+    out = np.zeros(1, DG_LAYOUT_DTYPE)
+    _check(lib().vit_data_groups_table_layout(_np(tab), tab.size, _np(out)), "vit_data_groups_table_layout")
+    return out[0]
+
+
+def data_groups_table_dev(d_bytes, d_rec, tab, d_dg, d_sum, d_data=None, stream=None):
+    """data_groups_dev over every stream of the table (DG_STREAM_DTYPE) in a fixed number of launches.  uint8 CUDA tensors
+    in the layout of data_groups_table_layout: d_dg DGROUP_REC_DTYPE records (stream k's from dg_index[k]), d_sum one
+    DGROUP_SUM_DTYPE record (32 bytes) per stream, d_data the streams' blocks (stream k's from data_offset[k]; None: every
+    stream records only); d_rec typically packet_table_dev's, with rec_index from its layout"""
+    tab = _dg_table(tab)
+    _check(lib().vit_data_groups_table_dev(_ptr(d_bytes), _ptr(d_rec), _np(tab), tab.size, _ptr(d_dg), _ptr(d_sum), _ptr(d_data),
+                                           _stream_ptr(stream)), "vit_data_groups_table_dev")
 
 
 def mci_fibs_dev(d_fibs, nfibs, G, d_sub, d_grp, d_fib_ok=None, d_status=None, stream=None):

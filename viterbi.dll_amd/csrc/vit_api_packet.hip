@@ -219,3 +219,89 @@ int vit_data_groups_host(const uint8_t* bytes, const vit_packet_rec* rec, int64_
     if (nslots > 0) vit_data_groups_host_impl(bytes, rec, nslots, dg, max_groups, sum, data, data_capacity);
     return VIT_OK;
 }
+
+namespace {
+
+// The data group table's rules, its layout (h_out optional) and the table as the kernels read it, without its geometry
+// (tab optional); false, with the error text naming the entry, if a rule is broken.
+bool dg_table(const char* who, const vit_dg_stream* h_tab, uint32_t nstreams, vit_dg_layout* h_out, VitDgTable* tab) {
+    if (!h_tab || nstreams < 1u || nstreams > VIT_DG_MAX_STREAMS) {
+        set_err("%s: bad arguments (nstreams=%u, 1 ... %u; h_tab)", who, nstreams, (unsigned)VIT_DG_MAX_STREAMS);
+        return false;
+    }
+    vit_dg_layout lay = {};
+    VitDgTable t = {};
+    uint64_t slots = 0;
+    for (uint32_t k = 0; k < nstreams; k++) {
+        const vit_dg_stream& s = h_tab[k];
+        const char* why = nullptr;
+        if (s.nslots < 1u || s.nslots > DG_MAX_SLOTS) why = "nslots must be 1 ... 1<<24";
+        else if (s.records_only > 1u) why = "records_only must be 0 or 1";
+        else if (s.records_only && s.data_capacity) why = "data_capacity must be 0 with records_only 1";
+        else if (s.offset + (uint64_t)SLOT * s.nslots < s.offset) why = "offset + 24*nslots must fit 64 bits";
+        else if (s.rec_index + s.nslots < s.rec_index) why = "rec_index + nslots must fit 64 bits";
+        else if (slots + s.nslots > (1ull << 26)) why = "the table holds more than 1<<26 slots (16 bytes of scratch per slot: 1 GiB)";
+        else if (lay.ndg > 0xFFFFFFFFull) why = "dg_index must stay below 2^32";
+        else if (lay.data_bytes > 0xFFFFFFFFull) why = "data_offset must stay below 2^32";
+        if (why) {
+            set_err("%s: bad arguments (entry %u: %s; offset=%llu rec_index=%llu nslots=%u max_groups=%u data_capacity=%u records_only=%u)",
+                    who, k, why, (unsigned long long)s.offset, (unsigned long long)s.rec_index, s.nslots, s.max_groups, s.data_capacity,
+                    s.records_only);
+            return false;
+        }
+        lay.dg_index[k] = lay.ndg;
+        lay.data_offset[k] = lay.data_bytes;
+        VitDgEntry& e = t.e[k];
+        e.offset = s.offset;
+        e.rec0 = s.rec_index;
+        e.nslots = s.nslots;
+        e.max_groups = s.max_groups;
+        e.capacity = s.data_capacity;
+        e.has_data = s.records_only ? 0u : 1u;
+        e.dg0 = (uint32_t)lay.ndg;
+        e.data0 = (uint32_t)lay.data_bytes;
+        slots += s.nslots;
+        lay.ndg += s.max_groups;
+        lay.data_bytes += ((uint64_t)s.data_capacity + DG_ALIGN - 1u) & ~(uint64_t)(DG_ALIGN - 1u);
+        lay.bytes_end = std::max(lay.bytes_end, s.offset + (uint64_t)SLOT * s.nslots);
+        lay.rec_end = std::max(lay.rec_end, s.rec_index + s.nslots);
+    }
+    t.nstreams = nstreams;
+    if (h_out) *h_out = lay;
+    if (tab) *tab = t;
+    return true;
+}
+
+}  // namespace
+
+int vit_data_groups_table_layout(const vit_dg_stream* h_tab, uint32_t nstreams, vit_dg_layout* h_out) {
+    if (!h_out) return bad_arg("vit_data_groups_table_layout: bad arguments (h_out)");
+    return dg_table("vit_data_groups_table_layout", h_tab, nstreams, h_out, nullptr) ? VIT_OK : VIT_ERR_ARG;
+}
+
+int vit_data_groups_table_dev(const uint8_t* d_bytes, const vit_packet_rec* d_rec, const vit_dg_stream* h_tab, uint32_t nstreams,
+                              vit_dgroup_rec* d_dg, vit_dgroup_summary* d_sum, uint8_t* d_data, void* stream) {
+    static const char* const who = "vit_data_groups_table_dev";
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    vit_dg_layout lay;
+    VitDgTable tab;
+    if (!dg_table(who, h_tab, nstreams, &lay, &tab)) return VIT_ERR_ARG;
+    bool wants_data = false;
+    for (uint32_t k = 0; k < nstreams; k++) wants_data = wants_data || (tab.e[k].has_data && tab.e[k].capacity > 0);
+    const char* why = nullptr;
+    if (!d_bytes || !d_rec || !d_sum) why = "NULL d_bytes, d_rec or d_sum";
+    else if (!d_dg && lay.ndg > 0) why = "d_dg may be NULL only when the layout's ndg is 0";
+    else if (!d_data && wants_data) why = "d_data may be NULL only when no entry with records_only 0 has a data_capacity";
+    else if (misaligned4(d_rec) || misaligned4(d_dg) || misaligned4(d_sum)) why = "d_rec, d_dg and d_sum must be 4-byte aligned";
+    if (why) return bad_arg("%s: bad arguments (%s)", who, why);
+    if (!d_data)  // every stream as with d_data NULL
+        for (uint32_t k = 0; k < nstreams; k++) tab.e[k].has_data = 0;
+    // Nothing below waits for the device or copies from it: a memset and the kernels on `stream`, between the scratch
+    // lease's wait and record.
+    const hipStream_t s = (hipStream_t)stream;
+    ScratchLease scratch;
+    const int rc = scratch.begin(vit_dg_table_geometry(&tab), 0, s);
+    if (rc != VIT_OK) return rc;
+    LAUNCHCHK("data group table launch failed: %s", vit_launch_data_groups_table(d_bytes, d_rec, tab, d_dg, d_sum, d_data, scratch.sym<void>(), s));
+    return scratch.end();
+}

@@ -234,7 +234,7 @@ struct VitEnsTable {
     uint32_t max_rsdims, pad[3];
     VitEnsEntry e[VIT_ENS_MAX_SUBCH];
 };
-// The lookup of every table that travels in the kernel arguments (VitEnsTable here, VitPktTable below):
+// The lookup of every table that travels in the kernel arguments (VitEnsTable and VitPktTable above, VitDgTable below):
 // vit_table_find<Entry, &Entry::start>(e, n, x) is the largest k < n with e[k].start <= x, for starts that do not
 // decrease and begin with e[0].start == 0.
 template <class Entry, uint32_t Entry::*START>
@@ -247,6 +247,41 @@ __host__ __device__ inline uint32_t vit_table_find(const Entry* e, uint32_t n, u
     }
     return lo;
 }
+// Data groups for a table of streams (vit_dgroup_table.hip; include/viterbi_amd.h, vit_dg_stream): the table as the kernels
+// read it, BY VALUE in the kernel arguments.  Entry k holds where stream k's bytes, records and outputs start, where its
+// scratch arrays start and where its share of each stage's workgroups starts; a workgroup finds its stream with
+// vit_table_find.  Every stream has at least one slot, so it owns at least one workgroup of every stage but the link
+// totals, whose share is derived: a stream of nchunks chunks owns nchunks - 1 of them, from chunk0 - k on.  The gather
+// numbers the groups that are written over the table on the device, from the streams' headers.  What else the kernels
+// need of a stream - the places of its scratch arrays behind scr0, its chunks and blocks - follows from nslots.
+struct VitDgEntry {
+    uint64_t offset;      // bytes from d_bytes
+    uint64_t rec0;        // first vit_packet_rec
+    uint32_t nslots;
+    uint32_t max_groups;
+    uint32_t capacity;
+    uint32_t has_data;    // 0: records only, as with d_data NULL
+    uint32_t dg0;         // first vit_dgroup_rec (vit_dg_layout.dg_index)
+    uint32_t data0;       // its block of d_data (vit_dg_layout.data_offset)
+    uint32_t scr0;        // its scratch arrays behind the table's headers, in units of 16 bytes from the scratch's start
+    uint32_t chunk0;      // first link workgroup column: one per 16384 slots (and per address)
+    uint32_t blk0;        // first presence, sums and place workgroup: one per 4096 slots
+    uint32_t pad;         // 0
+};
+struct VitDgTable {
+    uint32_t nstreams, nchunk, nblk;  // the totals
+    uint32_t ngat;                    // gather passes: max(1, min(max_groups, nslots)) per stream, the most groups it can write
+    VitDgEntry e[VIT_DG_MAX_STREAMS];
+};
+static_assert(sizeof(VitDgEntry) == 56 && sizeof(VitDgTable) == 16 + 56 * VIT_DG_MAX_STREAMS && sizeof(VitDgTable) + 64 <= 4096,
+              "3600 bytes: the table and the gather's six pointers fit the 4 KB of kernel arguments");
+// Fills scr0, chunk0, blk0 and the totals from the entries' nslots and max_groups; returns the scratch the launches
+// need: the streams' 256-byte headers back to back, then every stream's arrays.
+size_t vit_dg_table_geometry(VitDgTable* tab);
+// The launches of vit_data_groups_table_dev; the caller has checked every argument rule.  d_scratch: what
+// vit_dg_table_geometry returned, 16-byte aligned; the headers are cleared on the stream in front of the kernels.
+hipError_t vit_launch_data_groups_table(const uint8_t* d_bytes, const vit_packet_rec* d_rec, const VitDgTable& tab, vit_dgroup_rec* d_dg,
+                                        vit_dgroup_summary* d_sum, uint8_t* d_data, void* d_scratch, hipStream_t stream);
 // vit_ens_find<&VitEnsEntry::frame0>(tab, x): the sub-channel whose frames hold frame x < tab.nframes (rec0, pass0 alike)
 template <uint32_t VitEnsEntry::*START>
 __host__ __device__ inline uint32_t vit_ens_find(const VitEnsTable& tab, uint32_t x) {
