@@ -783,6 +783,113 @@ int vit_mci_ens_table(const vit_mci_subch h_sub[64], const uint32_t keep_pi[24],
                       vit_ens_subch *h_out, uint32_t *nsub, vit_punct_profile *h_profiles, uint32_t *nprofiles,
                       uint64_t *skipped);
 
+/* Service directory: which services an ensemble carries, what they are called, and where their packet-mode components
+ * lie - from the same FIBs, groups, d_fib_ok, G = 1 ... 4096 and ngroups as vit_mci_fibs_dev, whose FIG header rule
+ * (p+1+len > 30 is `malformed` and ends the FIB; len == 0 advances one byte) and end marker hold unchanged.  It builds the
+ * table that starts the packet chain (vit_packet_table_dev, vit_data_groups_table_dev) and ties a packet address to its
+ * service.  As above, the layouts are the library's definitions, written without the standard's text at hand; each
+ * constant stands once in csrc/vit_fig_fmt.h.
+ *
+ * The walk of one used FIB reads FIG type 0 extensions 2 and 3 and FIG type 1 extensions 0, 1 and 5, each only with
+ * len >= 1; everything else is passed over by its length.  t = b[p+1]; the body ends before e = p+1+len, q = p+2.
+ * A FIG 0/2 or 0/3 with C/N (t>>7) or OE ((t>>6)&1) set, and a FIG 1/0, 1/1 or 1/5 with bit 3 of t set, counts into n_next
+ * and is otherwise passed over; the others set their status bit, whatever they turn out to hold.
+ *   FIG 0/2   exactly the walk of vit_mci_fibs_dev: while q < e an identifier of 2 (P/D 0) or 4 (P/D 1) bytes, big-endian,
+ *             a count byte, nc = count & 15 components c0 c1 of 2 bytes; an identifier with its count byte, or a
+ *             component, that does not fit before e makes the FIG `malformed` and ends it; what was read before counts.
+ *             Each service header gives one service entry: key SId, value (P/D, count byte).  Each component with TMId
+ *             c0>>6 == 3 gives one component entry: key SCId = (c0&63)<<6 | c1>>2, value (SId, P/S (c1>>1)&1, CA c1&1).
+ *             TMId 0, 1 and 2 give none here.
+ *   FIG 0/3   while q < e: fewer than 5 bytes left is `malformed` and ends the FIG.  b = b[q ..]: SCId b0<<4 | b1>>4,
+ *             CAOrg flag b1&1 (bits 3..1 of b1 are ignored), DG flag b2>>7, DSCTy b2&63, SubChId b3>>2, packet address
+ *             (b3&3)<<8 | b4.  With the CAOrg flag set the entry has two more bytes, which are skipped; if they do not
+ *             fit before e the FIG is `malformed` and ends there, and this entry gives nothing.  Each entry gives one
+ *             location entry: key SCId, value loc (below).
+ *   FIG 1     charset t>>4, extension t&7.  The identifier, big-endian, is 2 bytes for extensions 0 and 1 and 4 bytes for
+ *             extension 5; 16 label bytes follow, then the 16-bit character flag field, big-endian.  len < 1 + idlen + 18
+ *             is `malformed` (the FIG gives nothing; the walk goes on behind it); further bytes are ignored.  Extension 0
+ *             gives the ensemble label entry: value (EId, label, chars, charset).  Extensions 1 and 5 give a label
+ *             entry: key SId, value (label, chars, charset).
+ * A 16-bit SId and a 32-bit SId share one 32-bit key space, compared as the numbers they are; P/D is part of the service
+ * entry's value, not of the key.
+ * Per group the entries are ordered by (FIB index, byte offset in the FIB).  For every key and kind the last entry wins;
+ * the group's other entries of that key and kind are counted as equal to the winner or different from it.
+ * Which keys get a record: the distinct SIds of the group's service and label entries, and separately the distinct
+ * SCIds of its component and location entries, each set in ascending order; the first VIT_DIR_MAX of a set get records,
+ * in that order.  If there are more the group's overflow flag for that table is set and the others leave no trace.
+ * Records beyond the number written are all 0.  The result does not depend on scheduling: two runs give the same bytes.
+ * A FIB holds at most 13 entries (one service header and 12 TMId-3 components), 9 service entries, 5 location entries,
+ * 1 label and 15 FIGs, so with G <= 4096 every count below stays inside 16 bits. */
+#define VIT_DIR_MAX 64
+typedef struct vit_mci_service {   /* 32 bytes; d_svc[g*64 + i], ascending sid; written completely */
+    uint32_t sid;
+    uint8_t  label[16];
+    uint16_t chars;                /* character flag field of the winning label */
+    uint8_t  flags;                /* bit 0 a label was seen, bit 1 a FIG 0/2 service entry was seen,
+                                      bit 2 P/D of the last one, bits 7..4 charset of the winning label */
+    uint8_t  count;                /* count byte of the last FIG 0/2 service entry, as it stands */
+    uint16_t n_label, n_label_other;     /* label entries equal to / different from the winner (label, chars, charset) */
+    uint16_t n_listed, n_listed_other;   /* service entries equal to / different from (P/D, count byte) */
+} vit_mci_service;
+typedef struct vit_mci_pktcomp {   /* 20 bytes; d_pkt[g*64 + i], ascending scid; written completely */
+    uint16_t scid;
+    uint16_t flags;                /* bit 0 a FIG 0/3 entry was seen, bit 1 a TMId-3 component was seen,
+                                      bit 2 P/S, bit 3 CA of the last one */
+    uint32_t loc;                  /* last FIG 0/3 entry: bits 5..0 SubChId, 15..6 packet address, 21..16 DSCTy,
+                                      bit 22 DG flag, bit 23 CAOrg flag; 0 if none */
+    uint32_t sid;                  /* of the last TMId-3 component naming this SCId; 0 if none */
+    uint16_t n_loc, n_loc_other, n_comp, n_comp_other;
+} vit_mci_pktcomp;
+typedef struct vit_mci_dir {       /* 40 bytes; d_dir[g]; written completely */
+    uint16_t eid, chars;           /* of the last FIG 1/0 */
+    uint8_t  label[16];
+    uint8_t  flags;                /* bit 0 a FIG 1/0 was seen, bit 1 more than 64 SIds, bit 2 more than 64 SCIds */
+    uint8_t  charset;
+    uint16_t n_label, n_label_other;     /* FIG 1/0 entries equal to / different from (eid, label, chars, charset) */
+    uint16_t nsvc, npkt;           /* records written in d_svc / d_pkt for this group */
+    uint16_t nfib_used, nfib_malformed, n_next, reserved[2];   /* (two reserved fields: records of whole dwords) */
+} vit_mci_dir;
+#define VIT_MCI_DIR_USED      0x01  /* d_status[i] of vit_mci_dir_dev: the FIB was walked (a FIB that is not used gets 0) */
+#define VIT_MCI_DIR_MALFORMED 0x02
+#define VIT_MCI_DIR_FIG02     0x04  /* a FIG 0/2, a FIG 0/3, a FIG 1/0, 1/1 or 1/5 of the current configuration was read */
+#define VIT_MCI_DIR_FIG03     0x08
+#define VIT_MCI_DIR_FIG1      0x10
+/* d_svc and d_pkt receive 64*ngroups records each, d_dir ngroups, d_status (may be NULL) nfibs bytes.  Argument rules and
+ * errors are those of vit_mci_fibs_dev: VIT_ERR_NO_DEVICE first; VIT_ERR_ARG with vit_last_error() for a NULL d_fibs,
+ * d_svc, d_pkt or d_dir, G outside 1 ... 4096, a negative nfibs, or a d_svc / d_pkt / d_dir that is not 4-byte aligned.
+ * nfibs == 0 returns VIT_OK and writes nothing.  Everything is enqueued on `stream` without synchronising; d_fibs may
+ * have any alignment and is only read, and no byte outside its 32*nfibs bytes.  One launch, shaped as vit_mci_fibs_dev's;
+ * a group of more than 256 FIBs is walked twice (csrc/vit_mci_dir.hip). */
+int vit_mci_dir_dev(const uint8_t *d_fibs, const uint8_t *d_fib_ok /* may be NULL */, int64_t nfibs, uint32_t G,
+                    vit_mci_service *d_svc, vit_mci_pktcomp *d_pkt, vit_mci_dir *d_dir,
+                    uint8_t *d_status /* may be NULL */, void *stream);
+/* Host only, needs no GPU: the same definition on host memory (no alignment rule; otherwise the same VIT_ERR_ARG). */
+int vit_mci_dir_host(const uint8_t *h_fibs, const uint8_t *h_fib_ok, int64_t nfibs, uint32_t G,
+                     vit_mci_service *h_svc, vit_mci_pktcomp *h_pkt, vit_mci_dir *h_dir, uint8_t *h_status);
+/* Host only: vit_mci_ens_table with the packet-mode sub-channels.  Every row vit_mci_ens_table gives is given unchanged.
+ * In addition a SubChId whose org is present in long form, whose EEP profile builds, which has NO comp and which at
+ * least one of the npkt records with bit 0 of flags set names in loc (bits 5..0) gives one row with RSDims = 0; it is then
+ * not in *skipped.  Rows stay in ascending SubChId order; bit (row index) of *packet_rows marks the added rows.  A
+ * SubChId that has a comp stays as vit_mci_ens_table makes it and is not marked.  With npkt == 0 (h_pkt may then be
+ * NULL) every output equals vit_mci_ens_table's and *packet_rows is 0.  VIT_ERR_ARG as vit_mci_ens_table, and for a NULL
+ * packet_rows, a NULL h_pkt with npkt > 0, or npkt > VIT_DIR_MAX. */
+int vit_mci_dir_ens_table(const vit_mci_subch h_sub[64], const vit_mci_pktcomp *h_pkt, uint32_t npkt,
+                          const uint32_t keep_pi[24], uint32_t keep_tail, vit_ens_subch *h_out, uint32_t *nsub,
+                          vit_punct_profile *h_profiles, uint32_t *nprofiles, uint64_t *skipped, uint64_t *packet_rows);
+/* Host only: the stream table of vit_packet_table_dev from the rows above, once the caller has filled nframes and
+ * vit_ensemble_layout has placed them: one vit_pkt_stream per marked row k, in row order, with offset =
+ * h_layout->work_offset[k], framebytes = framebits/8, nframes the row's, the given fec, phase 0, min_score (used with
+ * VIT_PKT_FEC_SEARCH; it must be 0 with VIT_PKT_FEC_NONE) and reserved 0.  h_out has room for 64 entries, *nstreams receives
+ * their number (0 if no row is marked), h_row_of_stream[s], if not NULL, the row of stream s.  The FEC scheme is not read
+ * from the FIC: fec is the caller's, VIT_PKT_FEC_NONE or VIT_PKT_FEC_SEARCH; VIT_PKT_FEC_PHASE is VIT_ERR_ARG, because
+ * one phase does not fit several streams.  VIT_ERR_ARG also for a NULL pointer, nsub outside 1 ... 64, a bit of packet_rows
+ * at or above nsub, a marked row whose RSDims is not 0, whose nframes is 0 or whose framebits/8 is no multiple of 24 in
+ * 24 ... 1152, and a non-zero min_score with VIT_PKT_FEC_NONE.  A table of one stream or more passes
+ * vit_packet_table_layout. */
+int vit_mci_pkt_table(const vit_ens_subch *h_rows, uint32_t nsub, const vit_ens_layout *h_layout, uint64_t packet_rows,
+                      uint32_t fec, uint32_t min_score, vit_pkt_stream h_out[64], uint32_t *nstreams,
+                      uint32_t *h_row_of_stream /* may be NULL */);
+
 /* From the FFT: differential demodulation, frequency de-interleaving, QPSK demapping and quantisation of whole
  * transmission frames (EN 300 401 clauses 14.5 - 14.7 seen from the receiver) - the step between an FFT on the device and
  * vit_decode_fic_dev / the ring of the *_ti_dev calls.

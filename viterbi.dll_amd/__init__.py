@@ -41,6 +41,7 @@ EXPORTS = [
     "vit_data_groups_dev", "vit_data_groups_host", "vit_packet_table_layout", "vit_packet_table_dev",
     "vit_data_groups_table_layout", "vit_data_groups_table_dev",
     "vit_mci_fibs_dev", "vit_mci_fibs_host", "vit_eep_profile", "vit_mci_ens_table",
+    "vit_mci_dir_dev", "vit_mci_dir_host", "vit_mci_dir_ens_table", "vit_mci_pkt_table",
     "vit_decode_stream_multi",
 ]
 MULTI_LOOPBACK = 0x1
@@ -113,6 +114,16 @@ MCI_GROUP_DTYPE = np.dtype([("eid", "<u2"), ("cif", "<u2"), ("flags", "u1"), ("r
                             ("nfib_malformed", "<u2"), ("n_ens_other", "<u2"), ("n_next", "<u2"), ("reserved2", "<u2")])
 MCI_USED, MCI_MALFORMED, MCI_FIG00, MCI_FIG01, MCI_FIG02 = 1, 2, 4, 8, 16
 MCI_MAX_G = 4096
+# service directory: vit_mci_service and vit_mci_pktcomp per (group, record), vit_mci_dir per group
+DIR_MAX = 64
+MCI_SERVICE_DTYPE = np.dtype([("sid", "<u4"), ("label", "u1", (16,)), ("chars", "<u2"), ("flags", "u1"), ("count", "u1"),
+                              ("n_label", "<u2"), ("n_label_other", "<u2"), ("n_listed", "<u2"), ("n_listed_other", "<u2")])
+MCI_PKTCOMP_DTYPE = np.dtype([("scid", "<u2"), ("flags", "<u2"), ("loc", "<u4"), ("sid", "<u4"), ("n_loc", "<u2"),
+                              ("n_loc_other", "<u2"), ("n_comp", "<u2"), ("n_comp_other", "<u2")])
+MCI_DIR_DTYPE = np.dtype([("eid", "<u2"), ("chars", "<u2"), ("label", "u1", (16,)), ("flags", "u1"), ("charset", "u1"),
+                          ("n_label", "<u2"), ("n_label_other", "<u2"), ("nsvc", "<u2"), ("npkt", "<u2"), ("nfib_used", "<u2"),
+                          ("nfib_malformed", "<u2"), ("n_next", "<u2"), ("reserved", "<u2", (2,))])
+MCI_DIR_USED, MCI_DIR_MALFORMED, MCI_DIR_FIG02, MCI_DIR_FIG03, MCI_DIR_FIG1 = 1, 2, 4, 8, 16
 
 # vit_ens_subch / vit_ens_layout of include/viterbi_amd.h: one entry per sub-channel of an ensemble, and where its blocks lie
 ENS_MAX_SUBCH = 64
@@ -321,6 +332,10 @@ def lib():
         L.vit_mci_fibs_host.argtypes = [vp, vp, C.c_int64, C.c_uint32, vp, vp, vp]
         L.vit_eep_profile.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, pp, vp]
         L.vit_mci_ens_table.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, vp]
+        L.vit_mci_dir_dev.argtypes = [vp, vp, C.c_int64, C.c_uint32, vp, vp, vp, vp, vp]
+        L.vit_mci_dir_host.argtypes = [vp, vp, C.c_int64, C.c_uint32, vp, vp, vp, vp]
+        L.vit_mci_dir_ens_table.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
+        L.vit_mci_pkt_table.argtypes = [vp, C.c_uint32, vp, C.c_uint64, C.c_uint32, C.c_uint32, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -780,6 +795,57 @@ def mci_ens_table(sub, keep_pi, keep_tail, max_profiles=64):
     _check(lib().vit_mci_ens_table(_np(sub), _np(pi), tail, _np(rows), C.byref(nsub), C.byref(profs), C.byref(nprof),
                                    C.byref(skipped)), "vit_mci_ens_table")
     return rows[:nsub.value].copy(), [profs[k] for k in range(nprof.value)], int(skipped.value)
+
+
+def mci_dir_dev(d_fibs, nfibs, G, d_svc, d_pkt, d_dir, d_fib_ok=None, d_status=None, stream=None):
+    """the service directory of nfibs 32-byte FIBs (uint8 CUDA tensors; d_fib_ok as for mci_fibs_dev), resolved per group of
+    G FIBs: 64 MCI_SERVICE_DTYPE records (32 bytes each, in d_svc), 64 MCI_PKTCOMP_DTYPE records (20 bytes each, in d_pkt)
+    and one MCI_DIR_DTYPE record (40 bytes, in d_dir) per group; d_status: one byte per FIB, optional"""
+    _check(lib().vit_mci_dir_dev(_ptr(d_fibs), _ptr(d_fib_ok), nfibs, G, _ptr(d_svc), _ptr(d_pkt), _ptr(d_dir), _ptr(d_status),
+                                 _stream_ptr(stream)), "vit_mci_dir_dev")
+
+
+def mci_dir_host(fibs, G, fib_ok=None):
+    """host, no GPU: the same definition -> (MCI_SERVICE_DTYPE array (ngroups, 64), MCI_PKTCOMP_DTYPE array (ngroups, 64),
+    MCI_DIR_DTYPE array (ngroups,), the status bytes)"""
+    fibs = np.ascontiguousarray(fibs, np.uint8).reshape(-1, 32)
+    n = fibs.shape[0]
+    ng = (n + G - 1) // G if 1 <= G <= MCI_MAX_G else 0
+    svc, pkt = np.zeros((ng, DIR_MAX), MCI_SERVICE_DTYPE), np.zeros((ng, DIR_MAX), MCI_PKTCOMP_DTYPE)
+    d, st = np.zeros(ng, MCI_DIR_DTYPE), np.zeros(n, np.uint8)
+    ok = None if fib_ok is None else np.ascontiguousarray(fib_ok, np.uint8).reshape(n)
+    _check(lib().vit_mci_dir_host(_np(fibs), None if ok is None else _np(ok), n, G, _np(svc), _np(pkt), _np(d), _np(st)),
+           "vit_mci_dir_host")
+    return svc, pkt, d, st
+
+
+def mci_dir_ens_table(sub, pkt, keep_pi, keep_tail, max_profiles=64):
+    """host, no GPU: mci_ens_table with the packet-mode sub-channels that the group's MCI_PKTCOMP_DTYPE records (pkt: the
+    first npkt of them, or None) name -> (rows, profiles, skipped, packet_rows: bit k marks row k as an added one)"""
+    sub = np.ascontiguousarray(np.asarray(sub, MCI_SUBCH_DTYPE).reshape(-1))
+    if sub.size != 64:
+        raise ValueError("a group has 64 records")
+    pkt = np.zeros(0, MCI_PKTCOMP_DTYPE) if pkt is None else np.ascontiguousarray(np.asarray(pkt, MCI_PKTCOMP_DTYPE).reshape(-1))
+    pi = _keep_vectors(keep_pi)
+    tail = punct_profile([(6, keep_tail)]).seg[0].keep
+    rows = np.zeros(64, ENS_SUBCH_DTYPE)
+    profs = (PunctProfile * max(max_profiles, 1))()
+    nsub, nprof, skipped, marked = C.c_uint32(0), C.c_uint32(max_profiles), C.c_uint64(0), C.c_uint64(0)
+    _check(lib().vit_mci_dir_ens_table(_np(sub), _np(pkt) if pkt.size else None, pkt.size, _np(pi), tail, _np(rows), C.byref(nsub),
+                                       C.byref(profs), C.byref(nprof), C.byref(skipped), C.byref(marked)), "vit_mci_dir_ens_table")
+    return rows[:nsub.value].copy(), [profs[k] for k in range(nprof.value)], int(skipped.value), int(marked.value)
+
+
+def mci_pkt_table(rows, layout, packet_rows, fec=PKT_FEC_NONE, min_score=0):
+    """host, no GPU: the rows of mci_dir_ens_table (nframes filled), their ensemble_layout record and the mask of packet rows
+    -> (PKT_STREAM_DTYPE table for packet_table_dev, one stream per marked row; the row of every stream)"""
+    rows = _ens_table(rows)
+    lay = np.ascontiguousarray(np.asarray(layout, ENS_LAYOUT_DTYPE).reshape(1))
+    tab, row_of = np.zeros(PKT_MAX_STREAMS, PKT_STREAM_DTYPE), np.zeros(PKT_MAX_STREAMS, np.uint32)
+    n = C.c_uint32(0)
+    _check(lib().vit_mci_pkt_table(_np(rows), rows.size, _np(lay), packet_rows, fec, min_score, _np(tab), C.byref(n), _np(row_of)),
+           "vit_mci_pkt_table")
+    return tab[:n.value].copy(), row_of[:n.value].copy()
 
 
 def cif_ring(d_ring, first_row):

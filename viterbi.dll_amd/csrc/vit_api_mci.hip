@@ -1,7 +1,8 @@
 // vit_api_mci.hip -- the C ABI of the multiplex configuration (include/viterbi_amd.h, "Multiplex configuration"): the
 // argument rules and the launch of vit_mci_fibs_dev, and the two host-only steps behind it - the EEP profile of a
 // sub-channel and the table for vit_ensemble_dev.  The kernel and the host twin are in vit_mci.hip, the format's constants
-// and the EEP rule in vit_fig_fmt.h.
+// and the EEP rule in vit_fig_fmt.h.  Behind them the service directory ("Service directory"): vit_mci_dir_dev and its
+// host twin (vit_mci_dir.hip), and the two host-only steps that lead from it to the table of vit_packet_table_dev.
 #include <string.h>
 
 #include "vit_fig_fmt.h"
@@ -79,22 +80,26 @@ int vit_eep_profile(uint32_t option, uint32_t level, uint32_t size_cu, const uin
     return VIT_OK;
 }
 
-int vit_mci_ens_table(const vit_mci_subch h_sub[64], const uint32_t keep_pi[24], uint32_t keep_tail, vit_ens_subch* h_out,
-                      uint32_t* nsub, vit_punct_profile* h_profiles, uint32_t* nprofiles, uint64_t* skipped) {
-    if (!h_sub || !h_out || !nsub || !h_profiles || !nprofiles || !skipped)
-        return bad_arg("vit_mci_ens_table: bad arguments (NULL pointer)");
+namespace {
+
+// vit_mci_ens_table (packet = 0, packet_rows = nullptr) and vit_mci_dir_ens_table: `packet` is the mask of the SubChIds
+// that a FIG 0/3 entry names; one of them without a component gives a row where the first call skips it
+int ens_table(const char* who, const vit_mci_subch* h_sub, uint64_t packet, const uint32_t* keep_pi, uint32_t keep_tail,
+              vit_ens_subch* h_out, uint32_t* nsub, vit_punct_profile* h_profiles, uint32_t* nprofiles, uint64_t* skipped,
+              uint64_t* packet_rows) {
     if (!vectors_ok(keep_pi, keep_tail))
-        return bad_arg("vit_mci_ens_table: bad arguments (keep_pi[i] must have 8+i+1 one bits, keep_tail 12 in its low 24)");
+        return bad_arg("%s: bad arguments (keep_pi[i] must have 8+i+1 one bits, keep_tail 12 in its low 24)", who);
     const uint32_t cap = *nprofiles;
     uint32_t rows = 0, nprof = 0;
-    uint64_t skip = 0;
+    uint64_t skip = 0, marked = 0;
     for (uint32_t c = 0; c < NSUBCH; c++) {
         const uint32_t org = h_sub[c].org, comp = h_sub[c].comp;
         if (!(org & ORG_PRESENT)) continue;
         vit_punct_profile prof;
         uint32_t fb = 0;
         const uint32_t size = (org >> ORG_SIZE_SHIFT) & ORG_SIZE_MASK;
-        if (!(org & ORG_LONG) || !(comp & COMP_PRESENT) ||
+        const bool has_comp = (comp & COMP_PRESENT) != 0, named = !has_comp && ((packet >> c) & 1u);
+        if (!(org & ORG_LONG) || !(has_comp || named) ||
             !eep_build((org >> ORG_OPTION_SHIFT) & ORG_OPTION_MASK, (org >> ORG_LEVEL_SHIFT) & ORG_LEVEL_MASK, size, keep_pi,
                        keep_tail, &prof, &fb)) {
             skip |= 1ull << c;
@@ -103,21 +108,104 @@ int vit_mci_ens_table(const vit_mci_subch h_sub[64], const uint32_t keep_pi[24],
         uint32_t k = 0;
         while (k < nprof && memcmp(&h_profiles[k], &prof, sizeof(prof)) != 0) k++;
         if (k == nprof) {
-            if (nprof == cap)
-                return bad_arg("vit_mci_ens_table: bad arguments (h_profiles holds %u profiles, SubChId %u needs one more)", cap, c);
+            if (nprof == cap) return bad_arg("%s: bad arguments (h_profiles holds %u profiles, SubChId %u needs one more)", who, cap, c);
             h_profiles[nprof++] = prof;
         }
-        const bool dabplus = (comp & COMP_TMID_MASK) == 0 && ((comp >> COMP_TYPE_SHIFT) & COMP_TYPE_MASK) == COMP_TYPE_DABPLUS;
+        const bool dabplus = has_comp && (comp & COMP_TMID_MASK) == 0 && ((comp >> COMP_TYPE_SHIFT) & COMP_TYPE_MASK) == COMP_TYPE_DABPLUS;
         vit_ens_subch row = {};
         row.col = CU_SYMBOLS * (org & ORG_START_MASK);
         row.profile = k;
         row.framebits = fb;
         row.RSDims = dabplus ? fb / DABPLUS_BITS : 0u;
         row.nsym = CU_SYMBOLS * size;
+        if (named) marked |= 1ull << rows;
         h_out[rows++] = row;
     }
     *nsub = rows;
     *nprofiles = nprof;
     *skipped = skip;
+    if (packet_rows) *packet_rows = marked;
+    return VIT_OK;
+}
+
+const char* dir_args_wrong(const void* fibs, int64_t nfibs, uint32_t G, const void* svc, const void* pkt, const void* dir) {
+    if (nfibs < 0) return "nfibs must not be negative";
+    if (G < 1u || G > MAX_G) return "G must be 1 ... 4096";
+    if (nfibs > 0 && (!fibs || !svc || !pkt || !dir)) return "NULL fibs, svc, pkt or dir";
+    return nullptr;
+}
+
+static_assert(sizeof(vit_mci_service) == 32 && sizeof(vit_mci_pktcomp) == 20 && sizeof(vit_mci_dir) == 40, "record sizes");
+
+}  // namespace
+
+int vit_mci_ens_table(const vit_mci_subch h_sub[64], const uint32_t keep_pi[24], uint32_t keep_tail, vit_ens_subch* h_out,
+                      uint32_t* nsub, vit_punct_profile* h_profiles, uint32_t* nprofiles, uint64_t* skipped) {
+    if (!h_sub || !h_out || !nsub || !h_profiles || !nprofiles || !skipped)
+        return bad_arg("vit_mci_ens_table: bad arguments (NULL pointer)");
+    return ens_table("vit_mci_ens_table", h_sub, 0, keep_pi, keep_tail, h_out, nsub, h_profiles, nprofiles, skipped, nullptr);
+}
+
+int vit_mci_dir_dev(const uint8_t* d_fibs, const uint8_t* d_fib_ok, int64_t nfibs, uint32_t G, vit_mci_service* d_svc,
+                    vit_mci_pktcomp* d_pkt, vit_mci_dir* d_dir, uint8_t* d_status, void* stream) {
+    if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
+    const char* why = dir_args_wrong(d_fibs, nfibs, G, d_svc, d_pkt, d_dir);
+    if (!why && nfibs > 0 && (misaligned4(d_svc) || misaligned4(d_pkt) || misaligned4(d_dir)))
+        why = "d_svc, d_pkt and d_dir must be 4-byte aligned";
+    if (why) return bad_arg("vit_mci_dir_dev: bad arguments (%s; nfibs=%lld G=%u)", why, (long long)nfibs, G);
+    LAUNCHCHK("service directory launch failed: %s",
+              vit_launch_mci_dir(d_fibs, d_fib_ok, nfibs, G, d_svc, d_pkt, d_dir, d_status, (hipStream_t)stream));
+    return VIT_OK;
+}
+
+int vit_mci_dir_host(const uint8_t* h_fibs, const uint8_t* h_fib_ok, int64_t nfibs, uint32_t G, vit_mci_service* h_svc,
+                     vit_mci_pktcomp* h_pkt, vit_mci_dir* h_dir, uint8_t* h_status) {
+    const char* why = dir_args_wrong(h_fibs, nfibs, G, h_svc, h_pkt, h_dir);
+    if (why) return bad_arg("vit_mci_dir_host: bad arguments (%s; nfibs=%lld G=%u)", why, (long long)nfibs, G);
+    if (nfibs > 0) vit_mci_dir_host_impl(h_fibs, h_fib_ok, nfibs, G, h_svc, h_pkt, h_dir, h_status);
+    return VIT_OK;
+}
+
+int vit_mci_dir_ens_table(const vit_mci_subch h_sub[64], const vit_mci_pktcomp* h_pkt, uint32_t npkt, const uint32_t keep_pi[24],
+                          uint32_t keep_tail, vit_ens_subch* h_out, uint32_t* nsub, vit_punct_profile* h_profiles,
+                          uint32_t* nprofiles, uint64_t* skipped, uint64_t* packet_rows) {
+    if (!h_sub || !h_out || !nsub || !h_profiles || !nprofiles || !skipped || !packet_rows || (npkt > 0 && !h_pkt))
+        return bad_arg("vit_mci_dir_ens_table: bad arguments (NULL pointer)");
+    if (npkt > DIR_MAX) return bad_arg("vit_mci_dir_ens_table: bad arguments (npkt=%u, at most 64)", npkt);
+    uint64_t packet = 0;
+    for (uint32_t i = 0; i < npkt; i++)
+        if (h_pkt[i].flags & PKT_LOC) packet |= 1ull << (h_pkt[i].loc & LOC_SUBCH_MASK);
+    return ens_table("vit_mci_dir_ens_table", h_sub, packet, keep_pi, keep_tail, h_out, nsub, h_profiles, nprofiles, skipped,
+                     packet_rows);
+}
+
+int vit_mci_pkt_table(const vit_ens_subch* h_rows, uint32_t nsub, const vit_ens_layout* h_layout, uint64_t packet_rows,
+                      uint32_t fec, uint32_t min_score, vit_pkt_stream h_out[64], uint32_t* nstreams, uint32_t* h_row_of_stream) {
+    if (!h_rows || !h_layout || !h_out || !nstreams) return bad_arg("vit_mci_pkt_table: bad arguments (NULL pointer)");
+    if (nsub < 1u || nsub > VIT_ENS_MAX_SUBCH) return bad_arg("vit_mci_pkt_table: bad arguments (nsub=%u, 1 ... 64)", nsub);
+    if (nsub < 64u && (packet_rows >> nsub)) return bad_arg("vit_mci_pkt_table: bad arguments (packet_rows marks a row at or above nsub=%u)", nsub);
+    if (fec != VIT_PKT_FEC_NONE && fec != VIT_PKT_FEC_SEARCH)
+        return bad_arg("vit_mci_pkt_table: bad arguments (fec=%u: VIT_PKT_FEC_NONE or VIT_PKT_FEC_SEARCH; one phase does not fit several streams)", fec);
+    if (fec == VIT_PKT_FEC_NONE && min_score) return bad_arg("vit_mci_pkt_table: bad arguments (min_score=%u without a search)", min_score);
+    for (uint32_t k = 0; k < nsub; k++) {
+        if (!((packet_rows >> k) & 1u)) continue;
+        const uint32_t fbytes = h_rows[k].framebits / 8u;
+        if (h_rows[k].RSDims || !h_rows[k].nframes || (h_rows[k].framebits & 7u) || fbytes % 24u || fbytes < 24u || fbytes > 1152u)
+            return bad_arg("vit_mci_pkt_table: bad arguments (row %u: RSDims=%u, 0; nframes=%u, >= 1; framebits=%u, framebits/8 a "
+                           "multiple of 24 in 24 ... 1152)", k, h_rows[k].RSDims, h_rows[k].nframes, h_rows[k].framebits);
+    }
+    uint32_t n = 0;
+    for (uint32_t k = 0; k < nsub; k++) {
+        if (!((packet_rows >> k) & 1u)) continue;
+        vit_pkt_stream s = {};
+        s.offset = h_layout->work_offset[k];
+        s.framebytes = h_rows[k].framebits / 8u;
+        s.nframes = h_rows[k].nframes;
+        s.fec = fec;
+        s.min_score = min_score;
+        if (h_row_of_stream) h_row_of_stream[n] = k;
+        h_out[n++] = s;
+    }
+    *nstreams = n;
     return VIT_OK;
 }

@@ -60,4 +60,32 @@ constexpr EepRule EEP_B[EEP_LEVELS] = {{24, -3, 0, 3, 10, 9}, {24, -3, 0, 3, 6, 
 constexpr uint32_t CU_SYMBOLS = 64;        // transmitted symbols (bits) of one capacity unit
 constexpr uint32_t DABPLUS_BITS = 192;     // framebits = 192 * RSDims
 
+// ---- the service directory (vit_mci_dir.hip; include/viterbi_amd.h, "Service directory"; the model is in
+// tests/test_mci_dir_host.py): FIG 0/2 (services, TMId-3 components), FIG 0/3 (packet-mode components), FIG 1/0, 1/1, 1/5
+constexpr uint32_t DIR_MAX = 64;           // records per group and table (VIT_DIR_MAX)
+constexpr uint32_t EXT_PACKET = 3;         // FIG 0/3
+constexpr uint32_t FIG1_EXT_MASK = 7, FIG1_OE = 0x08, FIG1_CHARSET_SHIFT = 4;
+constexpr uint32_t EXT_LABEL_ENS = 0, EXT_LABEL_SVC16 = 1, EXT_LABEL_SVC32 = 5;
+constexpr uint32_t LABEL_BYTES = 16, LABEL_VALUE_BYTES = 18;   // the label, and with its character flag field
+constexpr uint32_t TMID_PACKET = 3;
+constexpr uint32_t LOC_BYTES = 5, LOC_CAORG_BYTES = 2;
+// Entries one FIB can hold.  A FIG 0/2 costs 2 bytes of header; a service entry 3 at least (16-bit SId, count byte), a
+// component entry 2 behind its service's: 2 + 3k + 2(n - k) <= 30 gives n <= 13 with k = 1 (one service, 12 components),
+// and k <= 9 alone.  A location entry costs 5 bytes, (30 - 2) / 5 = 5.  A label costs 1 + 1 + 2 + 18 = 22 bytes: one, and
+// the 8 bytes beside it hold two more entries at most.  A FIG passed over costs 2 bytes at least, as above.
+constexpr uint32_t DIR_MAX_ENTRIES = 13, DIR_MAX_SVC_ENTRIES = 9, DIR_MAX_LOC_ENTRIES = 5, DIR_MAX_LABELS = 1;
+static_assert(2u + 3u + 2u * (DIR_MAX_ENTRIES - 1u) <= FIB_DATA && 2u + 3u + 2u * DIR_MAX_ENTRIES > FIB_DATA, "13 entries");
+static_assert(2u + 3u * DIR_MAX_SVC_ENTRIES <= FIB_DATA && 2u + 3u * (DIR_MAX_SVC_ENTRIES + 1u) > FIB_DATA, "9 services");
+static_assert(2u + LOC_BYTES * DIR_MAX_LOC_ENTRIES <= FIB_DATA && 2u + LOC_BYTES * (DIR_MAX_LOC_ENTRIES + 1u) > FIB_DATA, "5 locations");
+static_assert(2u + 2u + LABEL_VALUE_BYTES <= FIB_DATA && 2u * (2u + 2u + LABEL_VALUE_BYTES) > FIB_DATA, "1 label");
+static_assert(MAX_G * DIR_MAX_ENTRIES < 65536u && MAX_G * DIR_MAX_SVC_ENTRIES < 65536u && MAX_G * DIR_MAX_LOC_ENTRIES < 65536u &&
+              MAX_G * DIR_MAX_LABELS < 65536u, "counts are 16 bits");
+// vit_mci_service.flags, vit_mci_pktcomp.flags, vit_mci_pktcomp.loc, vit_mci_dir.flags
+constexpr uint32_t SVC_LABEL = 1, SVC_LISTED = 2, SVC_PD_SHIFT = 2, SVC_CHARSET_SHIFT = 4;
+constexpr uint32_t PKT_LOC = 1, PKT_COMP = 2, PKT_PS_SHIFT = 2, PKT_CA_SHIFT = 3;
+constexpr uint32_t LOC_SUBCH_MASK = 63, LOC_ADDR_SHIFT = 6, LOC_DSCTY_SHIFT = 16, LOC_DG_SHIFT = 22, LOC_CAORG_SHIFT = 23;
+constexpr uint32_t DIR_LABEL = 1, DIR_SVC_OVERFLOW = 2, DIR_PKT_OVERFLOW = 4;
+// d_status of vit_mci_dir_dev
+constexpr uint32_t ST_DIR_FIG02 = 4, ST_DIR_FIG03 = 8, ST_DIR_FIG1 = 16;
+
 }  // namespace figfmt

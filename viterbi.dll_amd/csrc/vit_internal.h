@@ -213,6 +213,12 @@ hipError_t vit_launch_mci(const uint8_t* d_fibs, const uint8_t* d_fib_ok, int64_
                           vit_mci_group* d_grp, uint8_t* d_status, hipStream_t stream);
 void vit_mci_fibs_host_impl(const uint8_t* h_fibs, const uint8_t* h_fib_ok, int64_t nfibs, uint32_t G, vit_mci_subch* h_sub,
                             vit_mci_group* h_grp, uint8_t* h_status);
+// Service directory (vit_mci_dir.hip); the caller has checked every argument rule.  One launch; the host form is the same
+// walk on host memory.
+hipError_t vit_launch_mci_dir(const uint8_t* d_fibs, const uint8_t* d_fib_ok, int64_t nfibs, uint32_t G, vit_mci_service* d_svc,
+                              vit_mci_pktcomp* d_pkt, vit_mci_dir* d_dir, uint8_t* d_status, hipStream_t stream);
+void vit_mci_dir_host_impl(const uint8_t* h_fibs, const uint8_t* h_fib_ok, int64_t nfibs, uint32_t G, vit_mci_service* h_svc,
+                           vit_mci_pktcomp* h_pkt, vit_mci_dir* h_dir, uint8_t* h_status);
 // RS(120,110) superframe check, one lane per column.
 // host_polls_ret (nsf == 1, rsdims <= 256): d_ret is host-visible and receives its value with system-scope release
 // semantics after the last output byte, so the host may spin on it instead of synchronising the stream.
