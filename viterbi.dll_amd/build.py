@@ -12,7 +12,7 @@ SOURCES = ["vit_api.hip", "vit_ring.hip", "vit_api_decode.hip", "vit_api_ens.hip
            "vit_iq_convert.hip", "vit_ofdm_acq.hip", "vit_ofdm_tii.hip", "vit_resample.hip", "vit_packet.hip", "vit_packet_table.hip", "vit_dgroup.hip", "vit_dgroup_table.hip", "vit_api_packet.hip",
            "vit_mci.hip", "vit_mci_dir.hip", "vit_api_mci.hip"]
 PK8_SOURCE = "vit_pk8.hip"  # round-3 experiment (8 frames per wavefront, slower): only with extra=["-DVIT_WITH_PK8"]
-DEPS = SOURCES + ["vit_internal.h", "vit_host.h", "rs_dev.h", "vit_pk_dev.h", "vit_pk_acs.h", "vit_pk_tb.h", "vit_pk_fixed.h", "vit_pk_long.h", "vit_punct_dev.h", "vit_fft_dev.h", "vit_iq_dev.h", "vit_csi_dev.h", "vit_demap_dev.h", "vit_wave_dev.h", "vit_crc_dev.h", "vit_packet_fmt.h", "vit_packet_dev.h", "vit_dgroup_dev.h", "vit_fec_block.inc","vit_image_dev.h", "vit_fig_fmt.h", "exports.map"]
+DEPS = SOURCES + ["vit_internal.h", "vit_host.h", "rs_dev.h", "vit_pk_dev.h", "vit_pk_acs.h", "vit_pk_tb.h", "vit_pk_fixed.h", "vit_pk_long.h", "vit_punct_dev.h", "vit_fft_dev.h", "vit_iq_dev.h", "vit_csi_dev.h", "vit_demap_dev.h", "vit_wave_dev.h", "vit_crc_dev.h", "vit_packet_fmt.h", "vit_packet_dev.h", "vit_dgroup_dev.h", "vit_fec_block.inc","vit_image_dev.h", "vit_fig_fmt.h", "vit_fib_group_dev.h", "exports.map"]
 
 
 def _stale():

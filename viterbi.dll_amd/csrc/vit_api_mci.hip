@@ -4,6 +4,7 @@
 // and the EEP rule in vit_fig_fmt.h.  Behind them the service directory ("Service directory"): vit_mci_dir_dev and its
 // host twin (vit_mci_dir.hip), and the two host-only steps that lead from it to the table of vit_packet_table_dev.
 #include <string.h>
+#include <initializer_list>
 
 #include "vit_fig_fmt.h"
 #include "vit_host.h"
@@ -12,14 +13,25 @@ using namespace figfmt;
 
 namespace {
 
-inline bool misaligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
+// The rule every FIB call shares, host and device form: VIT_OK, or bad_arg.  `outs` are the call's record pointers and
+// `names` says how the messages call them; the device forms (`device`) also want them 4-byte aligned.
+struct FibOutNames { const char *null, *misaligned; };
+constexpr FibOutNames MCI_OUTS = {"NULL fibs, sub or grp", "d_sub and d_grp must be 4-byte aligned"};
+constexpr FibOutNames DIR_OUTS = {"NULL fibs, svc, pkt or dir", "d_svc, d_pkt and d_dir must be 4-byte aligned"};
 
-// the rule every form of the FIB call shares; nullptr if the arguments are fine
-const char* mci_args_wrong(const void* fibs, int64_t nfibs, uint32_t G, const void* sub, const void* grp) {
-    if (nfibs < 0) return "nfibs must not be negative";
-    if (G < 1u || G > MAX_G) return "G must be 1 ... 4096";
-    if (nfibs > 0 && (!fibs || !sub || !grp)) return "NULL fibs, sub or grp";
-    return nullptr;
+int fib_args(const char* who, bool device, const void* fibs, int64_t nfibs, uint32_t G, std::initializer_list<const void*> outs,
+             const FibOutNames& names) {
+    bool null = !fibs, misaligned = false;
+    for (const void* p : outs) {
+        null = null || !p;
+        misaligned = misaligned || (reinterpret_cast<uintptr_t>(p) & 3u) != 0;
+    }
+    const char* why = nullptr;
+    if (nfibs < 0) why = "nfibs must not be negative";
+    else if (G < 1u || G > MAX_G) why = "G must be 1 ... 4096";
+    else if (nfibs > 0 && null) why = names.null;
+    else if (nfibs > 0 && device && misaligned) why = names.misaligned;
+    return why ? bad_arg("%s: bad arguments (%s; nfibs=%lld G=%u)", who, why, (long long)nfibs, G) : VIT_OK;
 }
 
 bool vectors_ok(const uint32_t* keep_pi, uint32_t keep_tail) {
@@ -53,9 +65,7 @@ bool eep_build(uint32_t option, uint32_t level, uint32_t size_cu, const uint32_t
 int vit_mci_fibs_dev(const uint8_t* d_fibs, const uint8_t* d_fib_ok, int64_t nfibs, uint32_t G, vit_mci_subch* d_sub,
                      vit_mci_group* d_grp, uint8_t* d_status, void* stream) {
     if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
-    const char* why = mci_args_wrong(d_fibs, nfibs, G, d_sub, d_grp);
-    if (!why && nfibs > 0 && (misaligned4(d_sub) || misaligned4(d_grp))) why = "d_sub and d_grp must be 4-byte aligned";
-    if (why) return bad_arg("vit_mci_fibs_dev: bad arguments (%s; nfibs=%lld G=%u)", why, (long long)nfibs, G);
+    if (int rc = fib_args("vit_mci_fibs_dev", true, d_fibs, nfibs, G, {d_sub, d_grp}, MCI_OUTS)) return rc;
     LAUNCHCHK("multiplex configuration launch failed: %s",
               vit_launch_mci(d_fibs, d_fib_ok, nfibs, G, d_sub, d_grp, d_status, (hipStream_t)stream));
     return VIT_OK;
@@ -63,8 +73,7 @@ int vit_mci_fibs_dev(const uint8_t* d_fibs, const uint8_t* d_fib_ok, int64_t nfi
 
 int vit_mci_fibs_host(const uint8_t* h_fibs, const uint8_t* h_fib_ok, int64_t nfibs, uint32_t G, vit_mci_subch* h_sub,
                       vit_mci_group* h_grp, uint8_t* h_status) {
-    const char* why = mci_args_wrong(h_fibs, nfibs, G, h_sub, h_grp);
-    if (why) return bad_arg("vit_mci_fibs_host: bad arguments (%s; nfibs=%lld G=%u)", why, (long long)nfibs, G);
+    if (int rc = fib_args("vit_mci_fibs_host", false, h_fibs, nfibs, G, {h_sub, h_grp}, MCI_OUTS)) return rc;
     if (nfibs > 0) vit_mci_fibs_host_impl(h_fibs, h_fib_ok, nfibs, G, h_sub, h_grp, h_status);
     return VIT_OK;
 }
@@ -128,13 +137,6 @@ int ens_table(const char* who, const vit_mci_subch* h_sub, uint64_t packet, cons
     return VIT_OK;
 }
 
-const char* dir_args_wrong(const void* fibs, int64_t nfibs, uint32_t G, const void* svc, const void* pkt, const void* dir) {
-    if (nfibs < 0) return "nfibs must not be negative";
-    if (G < 1u || G > MAX_G) return "G must be 1 ... 4096";
-    if (nfibs > 0 && (!fibs || !svc || !pkt || !dir)) return "NULL fibs, svc, pkt or dir";
-    return nullptr;
-}
-
 static_assert(sizeof(vit_mci_service) == 32 && sizeof(vit_mci_pktcomp) == 20 && sizeof(vit_mci_dir) == 40, "record sizes");
 
 }  // namespace
@@ -149,10 +151,7 @@ int vit_mci_ens_table(const vit_mci_subch h_sub[64], const uint32_t keep_pi[24],
 int vit_mci_dir_dev(const uint8_t* d_fibs, const uint8_t* d_fib_ok, int64_t nfibs, uint32_t G, vit_mci_service* d_svc,
                     vit_mci_pktcomp* d_pkt, vit_mci_dir* d_dir, uint8_t* d_status, void* stream) {
     if (hip_device_ready() != VIT_OK) return VIT_ERR_NO_DEVICE;
-    const char* why = dir_args_wrong(d_fibs, nfibs, G, d_svc, d_pkt, d_dir);
-    if (!why && nfibs > 0 && (misaligned4(d_svc) || misaligned4(d_pkt) || misaligned4(d_dir)))
-        why = "d_svc, d_pkt and d_dir must be 4-byte aligned";
-    if (why) return bad_arg("vit_mci_dir_dev: bad arguments (%s; nfibs=%lld G=%u)", why, (long long)nfibs, G);
+    if (int rc = fib_args("vit_mci_dir_dev", true, d_fibs, nfibs, G, {d_svc, d_pkt, d_dir}, DIR_OUTS)) return rc;
     LAUNCHCHK("service directory launch failed: %s",
               vit_launch_mci_dir(d_fibs, d_fib_ok, nfibs, G, d_svc, d_pkt, d_dir, d_status, (hipStream_t)stream));
     return VIT_OK;
@@ -160,8 +159,7 @@ int vit_mci_dir_dev(const uint8_t* d_fibs, const uint8_t* d_fib_ok, int64_t nfib
 
 int vit_mci_dir_host(const uint8_t* h_fibs, const uint8_t* h_fib_ok, int64_t nfibs, uint32_t G, vit_mci_service* h_svc,
                      vit_mci_pktcomp* h_pkt, vit_mci_dir* h_dir, uint8_t* h_status) {
-    const char* why = dir_args_wrong(h_fibs, nfibs, G, h_svc, h_pkt, h_dir);
-    if (why) return bad_arg("vit_mci_dir_host: bad arguments (%s; nfibs=%lld G=%u)", why, (long long)nfibs, G);
+    if (int rc = fib_args("vit_mci_dir_host", false, h_fibs, nfibs, G, {h_svc, h_pkt, h_dir}, DIR_OUTS)) return rc;
     if (nfibs > 0) vit_mci_dir_host_impl(h_fibs, h_fib_ok, nfibs, G, h_svc, h_pkt, h_dir, h_status);
     return VIT_OK;
 }

@@ -1,6 +1,7 @@
 // vit_fig_fmt.h -- every constant of the multiplex configuration (FIG 0/0, 0/1, 0/2 of EN 300 401 clause 6, the EEP rule
-// of clause 11.3.2) that the library restates, in one place: vit_mci.hip (kernel, host twin) and vit_api_mci.hip
-// (argument rules, profiles, the sub-channel table) take them from here, and include/viterbi_amd.h writes the same
+// of clause 11.3.2) that the library restates, in one place: vit_fib_group_dev.h (the walk over a FIB's FIGs, the FIG 0/2
+// service list), vit_mci.hip and vit_mci_dir.hip (kernels, host twins) and vit_api_mci.hip (argument rule, profiles, the
+// sub-channel table) take them from here, and include/viterbi_amd.h writes the same
 // definitions out in words ("Multiplex configuration").  They were written down without the standard's text at hand; a
 // correction against it is a change here plus the same change in the tests' model (tests/test_mci_host.py).
 #pragma once
@@ -25,6 +26,7 @@ static_assert(MAX_G * MAX_ENTRIES < 65536u && MAX_G * (FIB_DATA / 2u) < 65536u, 
 constexpr uint32_t FIG_LEN_MASK = 31, FIG_TYPE_SHIFT = 5;
 constexpr uint32_t FIG0_CN = 0x80, FIG0_OE = 0x40, FIG0_PD = 0x20, FIG0_EXT_MASK = 31;
 constexpr uint32_t EXT_ENSEMBLE = 0, EXT_SUBCH = 1, EXT_SERVICE = 2;
+constexpr uint32_t FIG02_NCOMP_MASK = 15;    // FIG 0/2, a service's count byte: the number of components that follow
 
 // vit_mci_subch.org
 constexpr uint32_t ORG_PRESENT = 1u << 31, ORG_LONG = 1u << 30;

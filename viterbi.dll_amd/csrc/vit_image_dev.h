@@ -1,5 +1,6 @@
-// vit_image_dev.h -- a run of bytes at any address into LDS with aligned 16-byte loads: the staging step that
-// vit_packet.hip (logical frames, FEC frames) and vit_mci.hip (FIBs) share.
+// vit_image_dev.h -- a run of bytes at any address into LDS with aligned 16-byte loads, and a lane's bytes out of that
+// image: the staging steps that the packet units (vit_packet_dev.h: logical frames, FEC frames) and the FIB group units
+// (vit_fib_group_dev.h: FIBs) share.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,4 +22,17 @@ __device__ __forceinline__ void load_image(const uint8_t* p, uint32_t n, uint8_t
             }
         }
     }
+}
+
+// The 4 * (NDW - 1) bytes at byte `base` of an LDS image into row[0 ... NDW-2]: NDW aligned dwords, one v_alignbyte per
+// dword, so the image holds a dword past the last byte taken.  (pkt_wave_records in vit_packet_dev.h keeps a sibling of
+// these lines, seven dwords into registers: through this routine its two kernels' instructions came out in another order.)
+template <uint32_t NDW>
+__device__ __forceinline__ void image_row(const uint8_t* s, uint32_t base, uint32_t* row) {
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(s + (base & ~3u));
+    uint32_t d[NDW];
+#pragma unroll
+    for (uint32_t k = 0; k < NDW; k++) d[k] = q[k];
+#pragma unroll
+    for (uint32_t k = 0; k < NDW - 1u; k++) row[k] = __builtin_amdgcn_alignbyte(d[k + 1u], d[k], base & 3u);
 }

@@ -3,40 +3,23 @@
 // group record (vit_mci_kernel), and its host twin (vit_mci_fibs_host_impl) over the same walk.  The definition is written
 // out in include/viterbi_amd.h ("Multiplex configuration"); every constant of the format is in vit_fig_fmt.h.
 //
-// Shape.  A workgroup of 256 lanes makes passes; a pass resolves four groups (G <= 64: a wavefront per group, a lane per
-// FIB) or one group (G > 64: tiles of 256 FIBs, a lane per FIB).  A tile's FIBs come into LDS as aligned 16-byte windows
-// (load_image: nothing outside the FIBs is read); each lane then takes its own FIB as nine dwords and one v_alignbyte per
-// dword into a row of 36 bytes - 9 dwords, odd, so the 64 lanes' byte reads at one offset meet on no bank - and walks it
-// there byte by byte (mci_walk: no register is indexed with a run-time value).  A lane leaves its entries, at most 12, as
-// two words each in LDS, entry j of lane l at [j][l].
-// Last wins, without depending on scheduling: the entries of a tile are ordered by the key (FIB of the tile, entry of the
-// FIB); three rounds between barriers - every entry raises its SubChId's key with an LDS atomic maximum, the entry whose
+// Shape: passes, tiles, a lane per FIB and the FIB's row in LDS are written out in vit_fib_group_dev.h, which this
+// kernel shares with vit_mci_dir_kernel.  Here a lane leaves at most 12 entries (mci_walk), and last wins, without depending on scheduling:
+// three rounds between barriers - every entry raises its SubChId's key with an LDS atomic maximum, the entry whose
 // key came out on top writes its value as the SubChId's reference, every entry compares itself with the reference and
 // adds to the equal or the other count.  Maximum and sums do not depend on the order of their operands.  A group of more
 // than one tile is taken from its last tile to its first: a SubChId whose reference is set by a later tile no longer raises
 // a key, and its earlier entries are only counted.  The 64 records stay in LDS across the tiles and are written once.
 //
-// Resources (hipcc -O3, gfx950, the compiler's report in profiles/r22_mci_resource_usage.txt): 81 VGPRs, 51,344 bytes of
-// LDS, no scratch, no spills; the LDS sets three workgroups per CU.  The stores are vector stores of plain C++.
-// A group is one workgroup's: with G = 4096 a call of 49152 FIBs runs on 12 workgroups.
+// Resources (hipcc -O3, gfx950, the compiler's report in profiles/r28_fib_group_resource_usage.txt): 81 VGPRs, 51,344
+// bytes of LDS, no scratch, no spills; the LDS sets three workgroups per CU.  The stores are vector stores of plain C++.
+// With G = 4096 a call of 49152 FIBs runs on 12 workgroups.
 #include <vector>
 
-#include "vit_fig_fmt.h"
-#include "vit_image_dev.h"
+#include "vit_fib_group_dev.h"
 #include "vit_internal.h"
 
 namespace {
-
-using namespace figfmt;
-typedef uint32_t u32;
-typedef uint64_t u64;
-constexpr u32 TPB = 256;
-constexpr u32 WAVE = 64;
-constexpr u32 SLOTS = TPB / WAVE;     // groups of a pass for G <= 64
-constexpr u32 TILE = TPB;             // FIBs of a tile for G > 64
-constexpr u32 ROW_DWORDS = 9;         // a lane's FIB in LDS: 32 bytes and one dword of skew
-constexpr u32 MAX_GRID = 1024;
-static_assert(NSUBCH == WAVE && TILE * MAX_ENTRIES < (1u << 16), "a lane per SubChId; keys");
 
 // an entry as two words: w0 = the value (org; SId; EId << 16 | cif), w1 = SubChId | kind << 6 | rest << 8 (comp's low ten
 // bits; change flags | Al << 2)
@@ -44,7 +27,10 @@ enum : u32 { E_ORG = 1, E_COMP = 2, E_ENS = 3 };
 constexpr u32 E_KIND_SHIFT = 6, E_REST_SHIFT = 8;
 
 // The walk of one used FIB, b[0 ... 29]: emit(kind, SubChId, w0, rest) for every entry in the order of their byte
-// offsets; n_next counts the FIGs passed over for C/N or OE; returns the status byte.
+// offsets; n_next counts the FIGs passed over for C/N or OE; returns the status byte.  The FIG iteration and the FIG 0/2
+// list are this walk's own text of what fib_walk and fig02_services (vit_fib_group_dev.h) state for dir_walk: through them
+// vit_mci_kernel ran 0.9 % (G = 12) and 1.2 % (G = 4096) slower on random FIBs, outside the timing rule
+// (profiles/HISTORY.md, round 28).  A change to the end marker, the overrun rule or the list's two exits goes into both.
 template <class Emit>
 __host__ __device__ __forceinline__ u32 mci_walk(const uint8_t* b, u32& n_next, Emit&& emit) {
     u32 st = ST_USED, p = 0;
@@ -133,7 +119,7 @@ __host__ __device__ __forceinline__ u32 mci_walk(const uint8_t* b, u32& n_next, 
 __global__ __launch_bounds__(TPB) void vit_mci_kernel(const uint8_t* __restrict__ fibs, const uint8_t* __restrict__ fib_ok,
                                                       long long nfibs, u32 G, long long ngroups, u32* __restrict__ sub,
                                                       u32* __restrict__ grp, uint8_t* __restrict__ status) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_img[TILE * FIB_BYTES + 32u];  // any phase, whole windows, a 9th dword
+    __shared__ __attribute__((aligned(16))) uint8_t s_img[IMG_BYTES];
     __shared__ u32 s_row[TPB * ROW_DWORDS];
     __shared__ u32 s_e0[MAX_ENTRIES][TPB], s_e1[MAX_ENTRIES][TPB];
     // per group of the pass and SubChId: the keys of the tile, the references, the counts
@@ -143,40 +129,21 @@ __global__ __launch_bounds__(TPB) void vit_mci_kernel(const uint8_t* __restrict_
     // per group: FIG 0/0 (s_ens1 = 1 << 31 | change flags | Al << 2 once one is seen) and the FIB counts
     __shared__ u32 s_ekey[SLOTS], s_ens0[SLOTS], s_ens1[SLOTS], s_nens_o[SLOTS], s_used[SLOTS], s_malf[SLOTS], s_next[SLOTS];
 
-    const u32 tid = threadIdx.x, lane = tid & (WAVE - 1u), wave = tid / WAVE;
-    const bool small = G <= WAVE;
-    const u32 gpp = small ? SLOTS : 1u;        // groups per pass
-    const u32 slot = small ? wave : 0u;        // this lane's FIB belongs to this group of the pass
-    const u32 os = tid / NSUBCH, oc = tid % NSUBCH;  // the (group of the pass, SubChId) this lane clears and writes out
-    const long long npasses = (ngroups + gpp - 1) / gpp;
-    // every lane of a workgroup makes the same passes and tiles: the barriers are uniform
-    for (long long pass = blockIdx.x; pass < npasses; pass += gridDim.x) {
+    const FibLanes L = fib_lanes(G, ngroups);
+    const u32 tid = L.tid, slot = L.slot, os = L.wave, oc = L.lane;  // (os, oc): the group of the pass and the SubChId to write out
+    for (long long pass = blockIdx.x; pass < L.npasses; pass += gridDim.x) {
         s_okey[os][oc] = s_ckey[os][oc] = s_org[os][oc] = s_comp[os][oc] = s_sid[os][oc] = 0;
         s_norg[os][oc] = s_norg_o[os][oc] = s_ncomp[os][oc] = s_ncomp_o[os][oc] = 0;
         if (oc == 0) s_ekey[os] = s_ens0[os] = s_ens1[os] = s_nens_o[os] = s_used[os] = s_malf[os] = s_next[os] = 0;
-        const long long g0 = pass * gpp, f0 = g0 * G;
-        const long long fe = f0 + (long long)gpp * G < nfibs ? f0 + (long long)gpp * G : nfibs;
-        const u32 total = (u32)(fe - f0);  // <= 4096
-        const u32 ntiles = (total + TILE - 1u) / TILE;  // 1 for G <= 64
-        for (u32 tile = ntiles; tile-- > 0;) {
-            const u32 t0 = tile * TILE, tn = total - t0 < TILE ? total - t0 : TILE;
-            const uint8_t* p = fibs + (u64)(f0 + t0) * FIB_BYTES;
-            load_image(p, tn * FIB_BYTES, s_img, tid, TPB);
+        const FibPass P = fib_pass(L, pass, G, nfibs);
+        for (u32 tile = P.ntiles; tile-- > 0;) {
+            const FibTile T = fib_tile(L, P, tile, G, fibs);
+            load_image(T.p, T.tn * FIB_BYTES, s_img, tid, TPB);
             __syncthreads();  // (also: the cleared records, and the previous tile's last round)
-            const u32 idx = small ? wave * G + lane : tid;  // this lane's FIB of the tile
-            const bool live = (!small || lane < G) && idx < tn;
-            const long long fib = f0 + t0 + idx;
-            const bool use = live && (!fib_ok || fib_ok[fib] != 0);
             u32 cnt = 0, st = 0, nnext = 0;
-            if (use) {
-                const u32 base = (u32)(reinterpret_cast<uintptr_t>(p) & 15u) + FIB_BYTES * idx, sh = base & 3u;
-                const u32* q = reinterpret_cast<const u32*>(s_img + (base & ~3u));
+            if (fib_in_use(T, fib_ok)) {
                 u32* row = s_row + ROW_DWORDS * tid;
-                u32 d[ROW_DWORDS];
-#pragma unroll
-                for (u32 k = 0; k < ROW_DWORDS; k++) d[k] = q[k];
-#pragma unroll
-                for (u32 k = 0; k < ROW_DWORDS - 1u; k++) row[k] = __builtin_amdgcn_alignbyte(d[k + 1u], d[k], sh);
+                image_row<ROW_DWORDS>(s_img, T.base, row);
                 st = mci_walk(reinterpret_cast<const uint8_t*>(row), nnext, [&](u32 kind, u32 c, u32 w0, u32 rest) {
                     if (cnt < MAX_ENTRIES) {
                         s_e0[cnt][tid] = w0;
@@ -184,12 +151,10 @@ __global__ __launch_bounds__(TPB) void vit_mci_kernel(const uint8_t* __restrict_
                         cnt++;
                     }
                 });
-                atomicAdd(&s_used[slot], 1u);
-                if (st & ST_MALFORMED) atomicAdd(&s_malf[slot], 1u);
-                if (nnext) atomicAdd(&s_next[slot], nnext);
+                fib_count(st, nnext, &s_used[slot], &s_malf[slot], &s_next[slot]);
             }
-            if (live && status) status[fib] = (uint8_t)st;
-            const u32 key0 = idx * 16u + 1u;
+            fib_status(T, st, status);
+            const u32 key0 = T.key0;
             // round 1: the last entry of the tile for every SubChId that has no reference yet
             for (u32 j = 0; j < cnt; j++) {
                 const u32 w1 = s_e1[j][tid], kind = (w1 >> E_KIND_SHIFT) & 3u, c = w1 & (NSUBCH - 1u);
@@ -236,8 +201,8 @@ __global__ __launch_bounds__(TPB) void vit_mci_kernel(const uint8_t* __restrict_
             if (oc == 0) s_ekey[os] = 0;
             __syncthreads();
         }
-        const long long g = g0 + os;
-        if (os < gpp && g < ngroups) {
+        const long long g = P.g0 + os;
+        if (os < L.gpp && g < ngroups) {
             u32* o = sub + 5u * ((u64)g * NSUBCH + oc);
             o[0] = s_org[os][oc];
             o[1] = s_comp[os][oc];
@@ -266,23 +231,13 @@ struct HostEntry {
 
 void vit_mci_fibs_host_impl(const uint8_t* h_fibs, const uint8_t* h_fib_ok, int64_t nfibs, uint32_t G, vit_mci_subch* h_sub,
                             vit_mci_group* h_grp, uint8_t* h_status) {
-    const int64_t ngroups = (nfibs + G - 1) / G;
+    const int64_t ngroups = fib_ngroups(nfibs, G);
     std::vector<HostEntry> ent;
     for (int64_t g = 0; g < ngroups; g++) {
-        const int64_t f0 = g * G, fe = f0 + G < nfibs ? f0 + G : nfibs;
         ent.clear();
-        u32 used = 0, malf = 0, next = 0;
-        for (int64_t f = f0; f < fe; f++) {
-            u32 st = 0;
-            if (!h_fib_ok || h_fib_ok[f]) {
-                st = mci_walk(h_fibs + FIB_BYTES * (u64)f, next, [&](u32 kind, u32 c, u32 w0, u32 rest) {
-                    ent.push_back(HostEntry{kind, c, w0, rest});
-                });
-                used++;
-                if (st & ST_MALFORMED) malf++;
-            }
-            if (h_status) h_status[f] = (uint8_t)st;
-        }
+        const FibCounts n = fib_group_host(h_fibs, h_fib_ok, nfibs, G, g, h_status, [&](const uint8_t* b, u32& next) {
+            return mci_walk(b, next, [&](u32 kind, u32 c, u32 w0, u32 rest) { ent.push_back(HostEntry{kind, c, w0, rest}); });
+        });
         vit_mci_subch* S = h_sub + NSUBCH * (u64)g;
         for (u32 c = 0; c < NSUBCH; c++) S[c] = vit_mci_subch{};
         vit_mci_group R = {};
@@ -316,10 +271,10 @@ void vit_mci_fibs_host_impl(const uint8_t* h_fibs, const uint8_t* h_fib_ok, int6
                 if ((e.w0 >> 16) != ens_eid || e.rest != ens_rest) nens_o++;
             }
         }
-        R.nfib_used = (uint16_t)used;
-        R.nfib_malformed = (uint16_t)malf;
+        R.nfib_used = (uint16_t)n.used;
+        R.nfib_malformed = (uint16_t)n.malf;
         R.n_ens_other = (uint16_t)nens_o;
-        R.n_next = (uint16_t)next;
+        R.n_next = (uint16_t)n.next;
         h_grp[g] = R;
     }
 }
@@ -327,10 +282,8 @@ void vit_mci_fibs_host_impl(const uint8_t* h_fibs, const uint8_t* h_fib_ok, int6
 hipError_t vit_launch_mci(const uint8_t* d_fibs, const uint8_t* d_fib_ok, int64_t nfibs, uint32_t G, vit_mci_subch* d_sub,
                           vit_mci_group* d_grp, uint8_t* d_status, hipStream_t stream) {
     if (nfibs <= 0) return hipSuccess;
-    const long long ngroups = (nfibs + G - 1) / G;
-    const long long npasses = G <= WAVE ? (ngroups + SLOTS - 1) / SLOTS : ngroups;
-    hipLaunchKernelGGL(vit_mci_kernel, dim3((unsigned)(npasses < (long long)MAX_GRID ? npasses : (long long)MAX_GRID)), dim3(TPB), 0,
-                       stream, d_fibs, d_fib_ok, (long long)nfibs, G, ngroups, reinterpret_cast<u32*>(d_sub),
-                       reinterpret_cast<u32*>(d_grp), d_status);
+    const long long ngroups = fib_ngroups(nfibs, G);
+    hipLaunchKernelGGL(vit_mci_kernel, fib_grid(ngroups, G), dim3(TPB), 0, stream, d_fibs, d_fib_ok, (long long)nfibs, G,
+                       ngroups, reinterpret_cast<u32*>(d_sub), reinterpret_cast<u32*>(d_grp), d_status);
     return hipGetLastError();
 }

@@ -4,12 +4,9 @@
 // (vit_mci_dir_kernel), and its host twin (vit_mci_dir_host_impl) over the same walk.  The definition is written out in
 // include/viterbi_amd.h ("Service directory"); every constant of the format is in vit_fig_fmt.h.
 //
-// Shape: that of vit_mci_kernel (vit_mci.hip, which this file leaves untouched - the staging is repeated here in its dozen
-// lines rather than shared, so that kernel's code and resource report stay what they were).  A workgroup of 256 lanes
-// makes passes; a pass resolves four groups (G <= 64: a wavefront per group, a lane per FIB) or one group (G > 64: tiles
-// of 256 FIBs, a lane per FIB).  A tile's FIBs come into LDS as aligned 16-byte windows (load_image), each lane takes its
-// own through v_alignbyte into a row of 9 dwords and walks it byte by byte (dir_walk), leaving at most 13 entries of two
-// words each, entry j of lane l at [j][l].  A label entry carries the offset of its 18 bytes in the lane's row, not a copy.
+// Shape: passes, tiles, a lane per FIB, the FIB's row in LDS and the walk over its FIGs are written out in
+// vit_fib_group_dev.h and shared with vit_mci_kernel (vit_mci.hip).  Here a lane leaves at most 13 entries (dir_walk); a
+// label entry carries the offset of its 18 bytes in the lane's row, not a copy.
 //
 // Which keys get records.  The records are keyed by SId (32 bits) and SCId (12 bits), so a group first agrees on its 64
 // smallest keys of each table: rounds between barriers, in round r every entry whose key lies above the key chosen in
@@ -25,38 +22,26 @@
 // group - a group of one tile (a transmission frame, or twenty) is walked once and its entries stay in LDS for both.
 // Carrying the set from tile to tile in one sweep would need every record shifted whenever an earlier tile brings a
 // smaller key.
-// Resolving is vit_mci_kernel's: three rounds between barriers per tile - every entry raises its record's key (FIB of the
-// tile, entry of the FIB) with an atomic maximum unless a later tile has set the reference, the entry whose key came out
-// on top writes its value as the reference (a label: its 18 bytes and charset as five words), every entry compares
-// itself with the reference, labels word by word in LDS, and adds to the equal or the other count.
+// Resolving is vit_mci_kernel's three rounds between barriers per tile (raise the key unless a later tile has set the
+// reference; write the reference; compare and count), per record and kind.  A label's value is its 18 bytes and charset
+// as five words, compared word by word in LDS.
 //
-// Resources (hipcc -O3, gfx950, the compiler's report in profiles/r27_mci_dir_resource_usage.txt): 121 VGPRs, 69,872
-// bytes of LDS (two workgroups per CU), no scratch, no VGPR spills; 16 scalars are parked in lanes of a VGPR at the head
-// of a pass and fetched at its end, none inside the loops over steps, rounds or entries.  The stores are vector stores of
-// plain C++.  A group is one workgroup's.
+// Resources (hipcc -O3, gfx950, the compiler's report in profiles/r28_fib_group_resource_usage.txt): 121 VGPRs, 69,872
+// bytes of LDS (two workgroups per CU), no scratch, no VGPR spills; 15 scalars are parked in lanes of a VGPR ahead of
+// the passes and fetched at a pass's head and end, none inside the loops over steps, rounds or entries.  The stores are
+// vector stores of plain C++.
 #include <algorithm>
 #include <string.h>
 #include <vector>
 
-#include "vit_fig_fmt.h"
-#include "vit_image_dev.h"
+#include "vit_fib_group_dev.h"
 #include "vit_internal.h"
 
 namespace {
 
-using namespace figfmt;
-typedef uint32_t u32;
-typedef uint64_t u64;
 typedef unsigned long long ull;
-constexpr u32 TPB = 256;
-constexpr u32 WAVE = 64;
-constexpr u32 SLOTS = TPB / WAVE;     // groups of a pass for G <= 64
-constexpr u32 TILE = TPB;             // FIBs of a tile for G > 64
-constexpr u32 ROW_DWORDS = 9;         // a lane's FIB in LDS: 32 bytes and one dword of skew
-constexpr u32 MAX_GRID = 1024;
 constexpr u32 LAB_WORDS = 5;          // a label value: 16 bytes, then 1 << 31 | charset << 16 | character flag field
 constexpr ull NONE = ~0ull;           // an idle cell of a key array: above every key
-static_assert(DIR_MAX == WAVE && DIR_MAX_ENTRIES <= 16u && TILE * 16u < (1u << 16), "a lane per record; round keys");
 
 // an entry as two words: w1 = kind | record index << 3 (filled in once the keys are chosen) | rest << 10
 //   E_SVC     w0 = SId, rest = P/D | count byte << 1           E_LABEL   w0 = SId, rest = offset in the FIB | charset << 5
@@ -71,86 +56,56 @@ constexpr u32 SEEN = 1u << 31;        // of every reference word
 // counts the FIGs passed over for C/N, OE or bit 3 of a label FIG; returns the status byte.
 template <class Emit>
 __host__ __device__ __forceinline__ u32 dir_walk(const uint8_t* b, u32& n_next, Emit&& emit) {
-    u32 st = ST_USED, p = 0;
-    while (p < FIB_DATA) {
-        const u32 h = b[p];
-        if (h == END_MARKER) break;
-        const u32 type = h >> FIG_TYPE_SHIFT, len = h & FIG_LEN_MASK;
-        if (p + 1u + len > FIB_DATA) {
-            st |= ST_MALFORMED;
-            break;
-        }
-        if (type <= 1u && len >= 1u) {
-            const u32 t = b[p + 1u], e = p + 1u + len;
-            u32 q = p + 2u;
-            if (type == 1u) {
-                const u32 ext = t & FIG1_EXT_MASK;
-                if (ext == EXT_LABEL_ENS || ext == EXT_LABEL_SVC16 || ext == EXT_LABEL_SVC32) {
-                    const u32 idlen = ext == EXT_LABEL_SVC32 ? 4u : 2u;
-                    if (t & FIG1_OE) {
-                        n_next++;
-                    } else {
-                        st |= ST_DIR_FIG1;
-                        if (len < 1u + idlen + LABEL_VALUE_BYTES) {
-                            st |= ST_MALFORMED;
-                        } else {
-                            u32 id = (u32)b[q] << 8 | b[q + 1u];
-                            if (idlen == 4u) id = id << 16 | (u32)b[q + 2u] << 8 | b[q + 3u];
-                            emit(ext == EXT_LABEL_ENS ? E_ELABEL : E_LABEL, id, (q + idlen) | (t >> FIG1_CHARSET_SHIFT) << R_CHARSET_SHIFT);
-                        }
-                    }
-                }
-            } else if ((t & FIG0_EXT_MASK) == EXT_SERVICE || (t & FIG0_EXT_MASK) == EXT_PACKET) {
-                if (t & (FIG0_CN | FIG0_OE)) {
+    return fib_walk(b, [&](u32 type, u32 p, u32 len) -> u32 {
+        if (type > 1u || len < 1u) return 0u;
+        const u32 t = b[p + 1u], e = p + 1u + len;
+        u32 q = p + 2u, st = 0;
+        if (type == 1u) {
+            const u32 ext = t & FIG1_EXT_MASK;
+            if (ext == EXT_LABEL_ENS || ext == EXT_LABEL_SVC16 || ext == EXT_LABEL_SVC32) {
+                const u32 idlen = ext == EXT_LABEL_SVC32 ? 4u : 2u;
+                if (t & FIG1_OE) {
                     n_next++;
-                } else if ((t & FIG0_EXT_MASK) == EXT_SERVICE) {
-                    st |= ST_DIR_FIG02;
-                    const u32 pd = (t & FIG0_PD) ? 1u : 0u, sidlen = pd ? 4u : 2u;
-                    bool fits = true;
-                    while (fits && q < e) {
-                        if (e - q < sidlen + 1u) {
-                            st |= ST_MALFORMED;
-                            break;
-                        }
-                        u32 sid = (u32)b[q] << 8 | b[q + 1u];
-                        if (sidlen == 4u) sid = sid << 16 | (u32)b[q + 2u] << 8 | b[q + 3u];
-                        const u32 count = b[q + sidlen], nc = count & 15u;
-                        emit(E_SVC, sid, pd | count << R_COUNT_SHIFT);
-                        q += sidlen + 1u;
-                        for (u32 c = 0; c < nc; c++) {
-                            if (e - q < 2u) {
-                                st |= ST_MALFORMED;
-                                fits = false;
-                                break;
-                            }
-                            const u32 c0 = b[q], c1 = b[q + 1u];
-                            if ((c0 >> 6) == TMID_PACKET)
-                                emit(E_COMP, sid, ((c0 & 63u) << 6 | c1 >> 2) | ((c1 >> 1) & 1u) << R_PS_SHIFT | (c1 & 1u) << R_CA_SHIFT);
-                            q += 2u;
-                        }
-                    }
                 } else {
-                    st |= ST_DIR_FIG03;
-                    while (q < e) {
-                        if (e - q < LOC_BYTES) {
-                            st |= ST_MALFORMED;
-                            break;
-                        }
-                        const u32 b1 = b[q + 1u], b2 = b[q + 2u], b3 = b[q + 3u], caorg = b1 & 1u;
-                        if (caorg && e - q < LOC_BYTES + LOC_CAORG_BYTES) {
-                            st |= ST_MALFORMED;
-                            break;
-                        }
-                        emit(E_LOC, (b3 >> 2) | ((b3 & 3u) << 8 | b[q + 4u]) << LOC_ADDR_SHIFT | (b2 & 63u) << LOC_DSCTY_SHIFT |
-                                        (b2 >> 7) << LOC_DG_SHIFT | caorg << LOC_CAORG_SHIFT, (u32)b[q] << 4 | b1 >> 4);
-                        q += LOC_BYTES + (caorg ? LOC_CAORG_BYTES : 0u);
+                    st |= ST_DIR_FIG1;
+                    if (len < 1u + idlen + LABEL_VALUE_BYTES)
+                        st |= ST_MALFORMED;
+                    else
+                        emit(ext == EXT_LABEL_ENS ? E_ELABEL : E_LABEL, fig_id(b + q, idlen),
+                             (q + idlen) | (t >> FIG1_CHARSET_SHIFT) << R_CHARSET_SHIFT);
+                }
+            }
+        } else if ((t & FIG0_EXT_MASK) == EXT_SERVICE || (t & FIG0_EXT_MASK) == EXT_PACKET) {
+            if (t & (FIG0_CN | FIG0_OE)) {
+                n_next++;
+            } else if ((t & FIG0_EXT_MASK) == EXT_SERVICE) {  // an entry per service, and its components with TMId 3, keyed by SCId
+                const u32 pd = (t & FIG0_PD) ? 1u : 0u;
+                st |= ST_DIR_FIG02 | fig02_services(
+                    b, q, e, pd, [&](u32 sid, u32 count) { emit(E_SVC, sid, pd | count << R_COUNT_SHIFT); },
+                    [&](u32 sid, u32 c0, u32 c1) {
+                        if ((c0 >> 6) == TMID_PACKET)
+                            emit(E_COMP, sid, ((c0 & 63u) << 6 | c1 >> 2) | ((c1 >> 1) & 1u) << R_PS_SHIFT | (c1 & 1u) << R_CA_SHIFT);
+                    });
+            } else {
+                st |= ST_DIR_FIG03;
+                while (q < e) {
+                    if (e - q < LOC_BYTES) {
+                        st |= ST_MALFORMED;
+                        break;
                     }
+                    const u32 b1 = b[q + 1u], b2 = b[q + 2u], b3 = b[q + 3u], caorg = b1 & 1u;
+                    if (caorg && e - q < LOC_BYTES + LOC_CAORG_BYTES) {
+                        st |= ST_MALFORMED;
+                        break;
+                    }
+                    emit(E_LOC, (b3 >> 2) | ((b3 & 3u) << 8 | b[q + 4u]) << LOC_ADDR_SHIFT | (b2 & 63u) << LOC_DSCTY_SHIFT |
+                                    (b2 >> 7) << LOC_DG_SHIFT | caorg << LOC_CAORG_SHIFT, (u32)b[q] << 4 | b1 >> 4);
+                    q += LOC_BYTES + (caorg ? LOC_CAORG_BYTES : 0u);
                 }
             }
         }
-        p += 1u + len;
-    }
-    return st;
+        return st;
+    });
 }
 
 // word k of the label value whose 18 bytes lie at r[0 ... 17]
@@ -171,7 +126,7 @@ __device__ __forceinline__ u32 find_key(const ull* a, ull k) {
 __global__ __launch_bounds__(TPB) void vit_mci_dir_kernel(const uint8_t* __restrict__ fibs, const uint8_t* __restrict__ fib_ok,
                                                           long long nfibs, u32 G, long long ngroups, u32* __restrict__ svc,
                                                           u32* __restrict__ pkt, u32* __restrict__ dir, uint8_t* __restrict__ status) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_img[TILE * FIB_BYTES + 32u];  // any phase, whole windows, a 9th dword
+    __shared__ __attribute__((aligned(16))) uint8_t s_img[IMG_BYTES];
     __shared__ u32 s_row[TPB * ROW_DWORDS];
     __shared__ u32 s_e0[DIR_MAX_ENTRIES][TPB], s_e1[DIR_MAX_ENTRIES][TPB];
     // per group of the pass: the chosen keys in ascending order; per record the keys of the tile, the references, the counts
@@ -185,15 +140,12 @@ __global__ __launch_bounds__(TPB) void vit_mci_dir_kernel(const uint8_t* __restr
     __shared__ u32 s_ekey[SLOTS], s_eid[SLOTS], s_elab[SLOTS][LAB_WORDS], s_ne[SLOTS], s_ne_o[SLOTS];
     __shared__ u32 s_ovf[SLOTS], s_used[SLOTS], s_malf[SLOTS], s_next[SLOTS];
 
-    const u32 tid = threadIdx.x, lane = tid & (WAVE - 1u), wave = tid / WAVE;
-    const bool small = G <= WAVE;
-    const u32 gpp = small ? SLOTS : 1u;        // groups per pass
-    const u32 slot = small ? wave : 0u;        // this lane's FIB belongs to this group of the pass
-    const u32 os = tid / DIR_MAX, oc = tid % DIR_MAX;  // the (group of the pass, record) this lane clears and writes out
-    const long long npasses = (ngroups + gpp - 1) / gpp;
-    const uint8_t* row8 = reinterpret_cast<const uint8_t*>(s_row + ROW_DWORDS * tid);
+    const FibLanes L = fib_lanes(G, ngroups);
+    const u32 tid = L.tid, slot = L.slot, gpp = L.gpp, os = L.wave, oc = L.lane;  // (os, oc): the group of the pass and the record to write out
+    u32* row = s_row + ROW_DWORDS * tid;
+    const uint8_t* row8 = reinterpret_cast<const uint8_t*>(row);
     // every lane of a workgroup makes the same passes, steps and rounds: the barriers are uniform
-    for (long long pass = blockIdx.x; pass < npasses; pass += gridDim.x) {
+    for (long long pass = blockIdx.x; pass < L.npasses; pass += gridDim.x) {
         s_sk[os][oc] = s_ck[os][oc] = NONE;
         s_vkey[os][oc] = s_lkey[os][oc] = s_pkey[os][oc] = s_okey[os][oc] = 0;
         s_sval[os][oc] = s_cfl[os][oc] = s_csid[os][oc] = s_loc[os][oc] = 0;
@@ -203,33 +155,17 @@ __global__ __launch_bounds__(TPB) void vit_mci_dir_kernel(const uint8_t* __restr
         s_np[os][oc] = s_np_o[os][oc] = s_no[os][oc] = s_no_o[os][oc] = 0;
         if (oc == 0) s_ekey[os] = s_eid[os] = s_ne[os] = s_ne_o[os] = s_ovf[os] = s_used[os] = s_malf[os] = s_next[os] = 0;
         if (oc < LAB_WORDS) s_elab[os][oc] = 0;
-        const long long g0 = pass * gpp, f0 = g0 * G;
-        const long long fe = f0 + (long long)gpp * G < nfibs ? f0 + (long long)gpp * G : nfibs;
-        const u32 total = (u32)(fe - f0);  // <= 4096
-        const u32 ntiles = (total + TILE - 1u) / TILE;  // 1 for G <= 64
+        const FibPass P = fib_pass(L, pass, G, nfibs);
         // one tile: a single step that chooses and resolves; more: a sweep that chooses, then one that resolves, backwards
-        const u32 nsteps = ntiles == 1u ? 1u : 2u * ntiles;
+        const u32 ntiles = P.ntiles, nsteps = ntiles == 1u ? 1u : 2u * ntiles;
         for (u32 step = 0; step < nsteps; step++) {
             const bool choose = step < ntiles, resolve = step + ntiles >= nsteps;
-            const u32 tile = choose ? step : nsteps - 1u - step;
-            const u32 t0 = tile * TILE, tn = total - t0 < TILE ? total - t0 : TILE;
-            const uint8_t* p = fibs + (u64)(f0 + t0) * FIB_BYTES;
-            load_image(p, tn * FIB_BYTES, s_img, tid, TPB);
+            const FibTile T = fib_tile(L, P, choose ? step : nsteps - 1u - step, G, fibs);
+            load_image(T.p, T.tn * FIB_BYTES, s_img, tid, TPB);
             __syncthreads();  // (also: the cleared records, and the previous step's last round)
-            const u32 idx = small ? wave * G + lane : tid;  // this lane's FIB of the tile
-            const bool live = (!small || lane < G) && idx < tn;
-            const long long fib = f0 + t0 + idx;
-            const bool use = live && (!fib_ok || fib_ok[fib] != 0);
             u32 cnt = 0, st = 0, nnext = 0;
-            if (use) {
-                const u32 base = (u32)(reinterpret_cast<uintptr_t>(p) & 15u) + FIB_BYTES * idx, sh = base & 3u;
-                const u32* q = reinterpret_cast<const u32*>(s_img + (base & ~3u));
-                u32* row = s_row + ROW_DWORDS * tid;
-                u32 d[ROW_DWORDS];
-#pragma unroll
-                for (u32 k = 0; k < ROW_DWORDS; k++) d[k] = q[k];
-#pragma unroll
-                for (u32 k = 0; k < ROW_DWORDS - 1u; k++) row[k] = __builtin_amdgcn_alignbyte(d[k + 1u], d[k], sh);
+            if (fib_in_use(T, fib_ok)) {
+                image_row<ROW_DWORDS>(s_img, T.base, row);
                 st = dir_walk(row8, nnext, [&](u32 kind, u32 w0, u32 rest) {
                     if (cnt < DIR_MAX_ENTRIES) {
                         s_e0[cnt][tid] = w0;
@@ -237,13 +173,9 @@ __global__ __launch_bounds__(TPB) void vit_mci_dir_kernel(const uint8_t* __restr
                         cnt++;
                     }
                 });
-                if (resolve) {
-                    atomicAdd(&s_used[slot], 1u);
-                    if (st & ST_MALFORMED) atomicAdd(&s_malf[slot], 1u);
-                    if (nnext) atomicAdd(&s_next[slot], nnext);
-                }
+                if (resolve) fib_count(st, nnext, &s_used[slot], &s_malf[slot], &s_next[slot]);
             }
-            if (resolve && live && status) status[fib] = (uint8_t)st;
+            if (resolve) fib_status(T, st, status);
             if (choose) {
                 // the keys chosen so far re-enter as candidates, a lane per key; the array starts idle again
                 const ull old_s = s_sk[os][oc], old_c = s_ck[os][oc];
@@ -300,7 +232,7 @@ __global__ __launch_bounds__(TPB) void vit_mci_dir_kernel(const uint8_t* __restr
             if (resolve) {
                 // every entry finds its record; round 1: the last entry of the tile for every record and kind that has no
                 // reference yet
-                const u32 key0 = idx * 16u + 1u;
+                const u32 key0 = T.key0;
                 for (u32 j = 0; j < cnt; j++) {
                     const u32 w0 = s_e0[j][tid], w1 = s_e1[j][tid], kind = w1 & E_KIND_MASK;
                     u32 i = 0;
@@ -375,7 +307,7 @@ __global__ __launch_bounds__(TPB) void vit_mci_dir_kernel(const uint8_t* __restr
             }
             __syncthreads();
         }
-        const long long g = g0 + os;
+        const long long g = P.g0 + os;
         if (os < gpp && g < ngroups) {  // (whole wavefronts: os is the wavefront)
             const ull ks = s_sk[os][oc], kc = s_ck[os][oc];
             const u32 nsvc = (u32)__popcll(__ballot(ks != NONE)), npkt = (u32)__popcll(__ballot(kc != NONE));
@@ -439,31 +371,22 @@ inline int key_index(const std::vector<u32>& keys, u32 k) {
 
 void vit_mci_dir_host_impl(const uint8_t* h_fibs, const uint8_t* h_fib_ok, int64_t nfibs, uint32_t G, vit_mci_service* h_svc,
                            vit_mci_pktcomp* h_pkt, vit_mci_dir* h_dir, uint8_t* h_status) {
-    const int64_t ngroups = (nfibs + G - 1) / G;
+    const int64_t ngroups = fib_ngroups(nfibs, G);
     std::vector<HostEntry> ent;
     std::vector<u32> sids, scids;
     for (int64_t g = 0; g < ngroups; g++) {
-        const int64_t f0 = g * G, fe = f0 + G < nfibs ? f0 + G : nfibs;
         ent.clear();
         sids.clear();
         scids.clear();
-        u32 used = 0, malf = 0, next = 0;
-        for (int64_t f = f0; f < fe; f++) {
-            u32 st = 0;
-            if (!h_fib_ok || h_fib_ok[f]) {
-                const uint8_t* b = h_fibs + FIB_BYTES * (u64)f;
-                st = dir_walk(b, next, [&](u32 kind, u32 w0, u32 rest) {
-                    HostEntry e = {kind, w0, rest, {}};
-                    if (kind == E_LABEL || kind == E_ELABEL) memcpy(e.lab, b + (rest & R_OFF_MASK), LABEL_VALUE_BYTES);
-                    if (kind == E_SVC || kind == E_LABEL) sids.push_back(w0);
-                    if (kind == E_COMP || kind == E_LOC) scids.push_back(ent_scid(e));
-                    ent.push_back(e);
-                });
-                used++;
-                if (st & ST_MALFORMED) malf++;
-            }
-            if (h_status) h_status[f] = (uint8_t)st;
-        }
+        const FibCounts n = fib_group_host(h_fibs, h_fib_ok, nfibs, G, g, h_status, [&](const uint8_t* b, u32& next) {
+            return dir_walk(b, next, [&](u32 kind, u32 w0, u32 rest) {
+                HostEntry e = {kind, w0, rest, {}};
+                if (kind == E_LABEL || kind == E_ELABEL) memcpy(e.lab, b + (rest & R_OFF_MASK), LABEL_VALUE_BYTES);
+                if (kind == E_SVC || kind == E_LABEL) sids.push_back(w0);
+                if (kind == E_COMP || kind == E_LOC) scids.push_back(ent_scid(e));
+                ent.push_back(e);
+            });
+        });
         vit_mci_service* S = h_svc + DIR_MAX * (u64)g;
         vit_mci_pktcomp* P = h_pkt + DIR_MAX * (u64)g;
         memset(S, 0, DIR_MAX * sizeof(*S));
@@ -537,9 +460,9 @@ void vit_mci_dir_host_impl(const uint8_t* h_fibs, const uint8_t* h_fib_ok, int64
         }
         D.nsvc = (uint16_t)sids.size();
         D.npkt = (uint16_t)scids.size();
-        D.nfib_used = (uint16_t)used;
-        D.nfib_malformed = (uint16_t)malf;
-        D.n_next = (uint16_t)next;
+        D.nfib_used = (uint16_t)n.used;
+        D.nfib_malformed = (uint16_t)n.malf;
+        D.n_next = (uint16_t)n.next;
         h_dir[g] = D;
     }
 }
@@ -547,10 +470,8 @@ void vit_mci_dir_host_impl(const uint8_t* h_fibs, const uint8_t* h_fib_ok, int64
 hipError_t vit_launch_mci_dir(const uint8_t* d_fibs, const uint8_t* d_fib_ok, int64_t nfibs, uint32_t G, vit_mci_service* d_svc,
                               vit_mci_pktcomp* d_pkt, vit_mci_dir* d_dir, uint8_t* d_status, hipStream_t stream) {
     if (nfibs <= 0) return hipSuccess;
-    const long long ngroups = (nfibs + G - 1) / G;
-    const long long npasses = G <= WAVE ? (ngroups + SLOTS - 1) / SLOTS : ngroups;
-    hipLaunchKernelGGL(vit_mci_dir_kernel, dim3((unsigned)(npasses < (long long)MAX_GRID ? npasses : (long long)MAX_GRID)), dim3(TPB),
-                       0, stream, d_fibs, d_fib_ok, (long long)nfibs, G, ngroups, reinterpret_cast<u32*>(d_svc),
-                       reinterpret_cast<u32*>(d_pkt), reinterpret_cast<u32*>(d_dir), d_status);
+    const long long ngroups = fib_ngroups(nfibs, G);
+    hipLaunchKernelGGL(vit_mci_dir_kernel, fib_grid(ngroups, G), dim3(TPB), 0, stream, d_fibs, d_fib_ok, (long long)nfibs, G,
+                       ngroups, reinterpret_cast<u32*>(d_svc), reinterpret_cast<u32*>(d_pkt), reinterpret_cast<u32*>(d_dir), d_status);
     return hipGetLastError();
 }
